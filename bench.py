@@ -1,6 +1,6 @@
 """bench.py — mel-spectrogram frames/sec on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the fused melspectrogram hot path over one batch of
 synthetic clips already resident in HBM.  Workload at every N (weak scaling: each
@@ -9,7 +9,12 @@ rank owns its own batch, no data-path collective — SURVEY.md §8e):
     headline: B=256 clips x 10 s @ 22.05 kHz per GPU, n_fft=2048 hop=512 n_mels=128
               hann, center, constant pad, power 2, Slaney  -> T=431 frames/clip
 
-Prints ONE JSON line (rank 0) with `roofline` and `cpu_baseline` objects.  Before the W warm-up steps
+Prints ONE JSON line (rank 0) with a `roofline` object.  A plain run does only what that line's headline needs:
+set-up, ramp, W warm-ups, the K timed steps and, with --dump-outputs DIR, the last timed step's output written as
+DIR/melspectrogram.npy (float32; past 64 MB a fixed, seeded sample of clips, their indices in
+DIR/melspectrogram_clips.npy).  Everything else it can measure runs only with --full, after the timed region:
+the `cpu_baseline` and `configs` objects, the power / clock sample (`roofline.secondary`) and, at N > 1 with
+--workload cfg5, the separately timed all-gather (`gather`).  Before the W warm-up steps
 the same step runs untimed for --ramp-seconds (default 1 s): a fresh box idles at ~600 MHz and the
 power management needs a few hundred ms of load to settle on the sustained clock (2.2-2.35 GHz at
 ~1 350 W for this kernel, tools/diag_clock.py); without it K = 20 steps of 0.2 ms time the ramp
@@ -58,12 +63,21 @@ def parse_args(argv=None):
     ap_.add_argument("--warmup", type=int, default=5)
     ap_.add_argument("--workload", default="headline", choices=sorted(WORKLOADS))
     ap_.add_argument("--batch", type=int, default=None, help="clips per GPU (default: workload's)")
-    ap_.add_argument("--no-cpu-baseline", action="store_true")
+    ap_.add_argument("--dump-outputs", metavar="DIR", default=None,
+                     help="after the timed steps, write what the last timed step computed (rank 0's mel "
+                          "spectrogram, float32) as DIR/melspectrogram.npy; past 64 MB a fixed, seeded sample of "
+                          "whole clips, whose indices go to DIR/melspectrogram_clips.npy")
+    ap_.add_argument("--full", action="store_true",
+                     help="after the timed region, also measure everything the headline does not need: the CPU "
+                          "baseline, every BASELINE config, the board-power / clock sample and (N > 1, cfg5) the "
+                          "all-gather of the outputs; the three options below switch parts of it off")
+    ap_.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap_.add_argument("--configs", default="all", choices=["all", "none"],
-                     help="N = 1 only, AFTER the headline's timed region: steady-state time, algorithmic GB/s and "
-                          "fraction of the HBM peak of every BASELINE config (tools/bench_configs.py) and the "
-                          "reference's published single-clip rows, embedded as `configs` in the JSON line")
-    ap_.add_argument("--no-power", action="store_true", help="skip the 2 s board-power / clock sample after the timed region")
+                     help="with --full, N = 1 only, AFTER the headline's timed region: steady-state time, algorithmic "
+                          "GB/s and fraction of the HBM peak of every BASELINE config (tools/bench_configs.py) and "
+                          "the reference's published single-clip rows, embedded as `configs` in the JSON line")
+    ap_.add_argument("--no-power", action="store_true",
+                     help="with --full: skip the 2 s board-power / clock sample after the timed region")
     ap_.add_argument("--ramp-seconds", type=float, default=1.0,
                      help="untimed pre-conditioning before the W warm-up steps: the same step run back to back "
                           "for this long so the GPU leaves its low-power state (a fresh box starts at ~600 MHz "
@@ -74,7 +88,12 @@ def parse_args(argv=None):
                           "barrier / max-over-ranks timing and the JSON contract without a GPU; the "
                           "line it prints is labelled and is not a measurement")
     ap_.add_argument("--stub-fail-rank", type=int, default=-1, help=argparse.SUPPRESS)
-    return ap_.parse_args(argv)
+    args = ap_.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap_.error("--steps must be >= 1 and --warmup >= 0")
+    if args.stub_step and args.dump_outputs:
+        ap_.error("--dump-outputs needs the real step (the stub computes nothing)")
+    return args
 
 
 # ----------------------------------------------------------------------------------------------
@@ -339,6 +358,26 @@ def _traffic_record(workload):
     return rec.get(workload), src or "profiles/traffic_latest.json (rocprofv3 --pmc passes, not measured in this run)"
 
 
+DUMP_BYTES_MAX = 64_000_000     # --dump-outputs budget (the headline's whole output is 56.5 MB)
+
+
+def dump_outputs(out, dirname):
+    """Write `out` (B, ...) float32 as dirname/melspectrogram.npy.  If it exceeds DUMP_BYTES_MAX, a sample of
+    whole clips drawn with a fixed seed is written instead (same clips for the same shape, every run) and
+    their indices go to melspectrogram_clips.npy (float64, exact)."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    B = out.shape[0]
+    per_clip = out[0].numel() * 4
+    if B * per_clip > DUMP_BYTES_MAX:
+        k = max(1, DUMP_BYTES_MAX // per_clip)
+        idx = np.sort(np.random.default_rng(0).choice(B, size=k, replace=False))
+        np.save(os.path.join(dirname, "melspectrogram_clips.npy"), idx.astype(np.float64))
+        out = out[idx.tolist()]
+    np.save(os.path.join(dirname, "melspectrogram.npy"), out.float().cpu().numpy())
+
+
 def main(argv=None):
     args = parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -419,7 +458,7 @@ def main(argv=None):
     if not stub:
         ev0.record()      # torch's current stream == the stream the kernels are enqueued on
     for i in range(args.steps):
-        step(i)
+        out = step(i)
     if not stub:
         ev1.record()
     barrier()
@@ -429,9 +468,13 @@ def main(argv=None):
     wall = sharding.max_over_ranks(wall, device=device)        # slowest rank decides
     dev_ms = sharding.max_over_ranks(dev_ms, device=device)
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)                   # what the last timed step handed its caller
+    del out
+
     # optional final gather of the outputs: timed on its own, never part of `value`
     gather_ms = None
-    if dist is not None and args.workload == "cfg5":
+    if args.full and dist is not None and args.workload == "cfg5":
         outs = step(0) if not stub else torch.zeros((4, n_mels, 16))      # (stub: the collective itself, on gloo)
         sync()
         buf = [torch.empty_like(outs) for _ in range(world)]
@@ -443,7 +486,7 @@ def main(argv=None):
         gather_ms = sharding.max_over_ranks((time.perf_counter() - tg) * 1e3, device=device)
         del buf
     power = None
-    if rank == 0 and world == 1 and not stub and not args.no_power:
+    if args.full and rank == 0 and world == 1 and not stub and not args.no_power:
         power = sample_power(step, sync)
 
     if rank == 0:
@@ -500,7 +543,7 @@ def main(argv=None):
         if stub:
             rec["data"] = "stub (launcher test: no kernel ran, not a measurement)"
             rec["roofline"] = None
-        if world == 1 and not stub and args.configs == "all":
+        if args.full and world == 1 and not stub and args.configs == "all":
             # every other BASELINE config + the reference's published rows, driver-timed in the same run
             try:
                 del batches
@@ -510,7 +553,7 @@ def main(argv=None):
                 rec["configs"]["published_rows"] = bench_configs.published_rows()
             except Exception as e:  # pragma: no cover - the headline line is the contract
                 rec["configs"] = {"error": repr(e)}
-        if world == 1 and not args.no_cpu_baseline and not stub:
+        if args.full and world == 1 and not args.no_cpu_baseline and not stub:
             rec["cpu_baseline"] = cpu_baseline(sr, n_fft, hop, n_mels, L)
         print(json.dumps(rec), flush=True)
     if dist is not None:

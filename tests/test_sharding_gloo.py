@@ -148,7 +148,7 @@ def test_bench_cfg5_workload_and_separate_gather():
     """BASELINE config 5 as a bench workload (512 clips x 30 s @16 kHz per GPU, Whisper mel parameters): two gloo
     ranks with the no-op step; the final all-gather of the outputs is timed on its own and never enters `value`."""
     import json
-    r = _run_bench("--gpus", "2", "--steps", "2", "--warmup", "1", "--stub-step", "--workload", "cfg5")
+    r = _run_bench("--gpus", "2", "--steps", "2", "--warmup", "1", "--stub-step", "--workload", "cfg5", "--full")
     assert r.returncode == 0, r.stderr[-2000:]
     rec = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     assert rec["n_gpus"] == 2 and rec["config"]["clips_per_gpu"] == 512 and rec["config"]["frames_per_clip"] == 3001

@@ -1,6 +1,6 @@
 """Every BASELINE.json config on ONE MI355X, steady state, plus the reference's published single-clip
-rows.  Used two ways: `python tools/bench_configs.py` prints the report, and bench.py embeds the same
-report as the `configs` object of its JSON line (after its own timed region, so `value` is untouched).
+rows.  Used two ways: `python tools/bench_configs.py` prints the report, and `bench.py --full` embeds the
+same report as the `configs` object of its JSON line (after its own timed region, so `value` is untouched).
 
   head  batch=256 x 10 s @22.05kHz melspectrogram / stft / istft n_fft=2048 hop=512 n_mels=128
   cfg2  batch=256 x 10 s @16 kHz   melspectrogram n_fft=400 hop=160 n_mels=80 (Whisper)
