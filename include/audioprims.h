@@ -238,6 +238,28 @@ int ap_istft_rows_f32(const float *S /*dev (B,F,row_stride,2)*/, int64_t B, int6
                       int n_fft, int hop, const float *window /*dev*/, const float *tw /*dev*/,
                       int64_t out_offset, int64_t out_len, float *out /*dev (B,out_len)*/, void *stream);
 
+/* Streaming ISTFT (center=False frames; the centre trim is the caller's lo / hi).  A call feeds T frames
+ * whose absolute index starts at frame0 (frames fed by the earlier calls); with K = frame0 + T every sample
+ * p < K*hop is finished.  The call
+ *   - starts each sample's sum from carry_in, the unnormalised partial sums of samples
+ *     [frame0*hop, frame0*hop + n_fft - hop) (ignored, may be NULL, when frame0 == 0),
+ *   - adds its frames' windowed inverse transforms in increasing frame order,
+ *   - writes out[b, p - lo] = sum / max(sum of w^2 over the frames 0..min(p/hop, K-1) touching p, 1e-8)
+ *     for p in [lo, hi), where frame0*hop <= lo <= hi <= K*hop, or <= (K-1)*hop + n_fft when final_ = 1
+ *     (the pending tail, normalised with the end-of-stream envelope),
+ *   - unless final_, writes carry_out: the partial sums of samples [K*hop, K*hop + n_fft - hop).
+ * Concatenated over any chunking the outputs are bit-identical.  0 < hop <= n_fft; T may be 0 (flush);
+ * S rows are row_stride >= T complex values apart, batch stride F*row_stride.  carry_out must not alias
+ * carry_in.  No allocation, no synchronisation, no state across calls.  n_fft 2048 / 1024 / 512 / 400 /
+ * 256: one fused launch, no workspace; other n_fft: row_stride == T, ap_irfft_frames_f32 into frames_ws
+ * (ap_istft_stream_workspace_floats(...) floats) and a carried overlap-add (two launches). */
+int64_t ap_istft_stream_workspace_floats(int64_t B, int64_t T, int n_fft, int hop);
+int ap_istft_stream_f32(const float *S /*dev (B,F,row_stride,2)*/, int64_t B, int64_t T, int64_t row_stride,
+                        int n_fft, int hop, const float *window /*dev*/, const float *tw /*dev*/, int64_t frame0,
+                        const float *carry_in /*dev (B,n_fft-hop)*/, float *carry_out /*dev (B,n_fft-hop)*/,
+                        int final_, int64_t lo, int64_t hi, float *frames_ws /*dev or NULL*/,
+                        float *out /*dev (B,hi-lo)*/, void *stream);
+
 /* resample_poly core: x (B,L) -> out (B, n_out), n_out = ceil(L*up/down),
  *   out[b,o] = sum_i taps[t - up*i] * x[b,i],  t = (o + n_pre_remove)*down,
  * float32 accumulation in increasing i like SciPy's upfirdn (padtype "constant").

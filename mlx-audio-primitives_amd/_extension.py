@@ -48,6 +48,7 @@ ABI_SYMBOLS = [
     "ap_mel_plan_words", "ap_mel_plan_host",
     "ap_pad_f32", "ap_frame_f32", "ap_overlap_add_f32",
     "ap_stft_f32", "ap_stft_rows_f32", "ap_melspec_f32", "ap_melspec_max_f32", "ap_melspec_rows_fused", "ap_melspec_rows_f32", "ap_irfft_frames_f32", "ap_istft_f32", "ap_istft_rows_f32", "ap_istft_workspace_floats",
+    "ap_istft_stream_f32", "ap_istft_stream_workspace_floats",
     "ap_magnitude_f32", "ap_phase_f32", "ap_complex_unary_rows_f32",
     "ap_resample_poly_ntaps", "ap_resample_poly_taps_host", "ap_resample_poly_f32",
     "ap_extend_f32", "ap_resample_poly_pad_samples", "ap_resample_poly_padded_f32", "ap_resample_fft_chirp_f32",
@@ -89,6 +90,7 @@ def _declare(lib) -> None:
         "ap_irfft_frames_f32": [P, L, L, I, P, P, P],
         "ap_istft_f32": [P, L, L, I, I, P, P, P, L, L, P, P],
         "ap_istft_rows_f32": [P, L, L, L, I, I, P, P, L, L, P, P],
+        "ap_istft_stream_f32": [P, L, L, L, I, I, P, P, L, P, P, I, L, L, P, P, P],
         "ap_magnitude_f32": [P, L, P, P],
         "ap_complex_unary_rows_f32": [P, L, L, L, I, P, P],
         "ap_resample_poly_ntaps": [I, I],
@@ -136,6 +138,8 @@ def _declare(lib) -> None:
     lib.ap_mel_plan_words.restype = L
     lib.ap_istft_workspace_floats.argtypes = [L, L, I, I, L]
     lib.ap_istft_workspace_floats.restype = L
+    lib.ap_istft_stream_workspace_floats.argtypes = [L, L, I, I]
+    lib.ap_istft_stream_workspace_floats.restype = L
     lib.ap_autocorrelation_nfft.argtypes = [L]
     lib.ap_autocorrelation_nfft.restype = L
     lib.ap_resample_poly_pad_samples.restype = L

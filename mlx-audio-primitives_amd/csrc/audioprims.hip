@@ -209,7 +209,7 @@ static int ap_launch_irfft8(const ApIrfftParams &P, int64_t B, void *stream, boo
 
 extern "C" {
 
-int ap_version(void) { return 100; }
+int ap_version(void) { return 101; }
 
 #ifdef AP_DIAG_STAMPS
 // diagnostic build only: copy the per-wave (shader cycles, 100 MHz ticks) stamps to the host

@@ -1,5 +1,5 @@
-"""Chunked (streaming) STFT / mel front end (the reference only lists
-"Streaming support - process audio in chunks" as future work, ARCHITECTURE.md:537-540).
+"""Chunked (streaming) STFT / mel front end and its inverse (the reference only
+lists "Streaming support - process audio in chunks" as future work, ARCHITECTURE.md:537-540).
 
 A stream is framed WITHOUT centring: frame t covers samples [t*hop, t*hop + n_fft) of the
 concatenation of every chunk fed so far.  Each ``process(chunk)`` call returns exactly the frames the
@@ -8,15 +8,20 @@ outputs over any chunking equals ``stft(whole, center=False)`` / ``melspectrogra
 center=False)`` bit for bit; only the n_fft - hop (or fewer) samples that later frames still need stay
 in HBM between calls.  ``center=True`` semantics are obtained by feeding n_fft//2 zeros first and
 calling ``flush()`` (which pads n_fft//2 zeros) at the end.
+
+``StreamingISTFT`` is the synthesis half: spectrum frames fed in chunks come back as the samples they
+finish, bit-identical over any chunking and equal to the offline ``istft`` of all frames; the unnormalised
+overlap-add tail (n_fft - hop samples per stream) stays in HBM between calls (ap_istft_stream_f32).
 """
 
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 from . import _extension as _x
 from .mel import melspectrogram
-from .stft import _resolve_stft_args, stft
+from .stft import _get_padded_window, _get_twiddles, _padded_row_stride, _resolve_stft_args, stft
 
 
 class StreamingSTFT:
@@ -93,3 +98,106 @@ class StreamingSTFT:
 
     def reset(self) -> None:
         self._tail, self._one_d, self._started, self.frames_emitted = None, None, False, 0
+
+
+class StreamingISTFT:
+    """Incremental ``istft``: feed (F, T) or (B, F, T) spectrum chunks (T may be 0), get the samples they finish.
+
+    After K frames every sample p < K*hop is final, so ``process`` returns the samples the chunk finished
+    ((n,) or (B, n), possibly n = 0) and ``flush()`` the pending n_fft - hop, normalised with the end-of-stream
+    envelope.  The concatenation equals ``istft(S_all, center=center)`` (no ``length``: trim it yourself);
+    ``center=True`` drops n_fft//2 samples at the start and at the flush.  The carry lives in two device
+    buffers used in turn; nothing is synchronised and nothing is read back."""
+
+    def __init__(self, n_fft: int = 2048, hop_length: int | None = None, win_length: int | None = None,
+                 window="hann", center: bool = False):
+        self.n_fft = int(n_fft)
+        self.hop_length, self.win_length = _resolve_stft_args(self.n_fft, hop_length, win_length)
+        self.window = window
+        self.center = bool(center)
+        if self.center and self.hop_length > self.n_fft - self.n_fft // 2:
+            raise ValueError(f"center=True needs hop_length <= n_fft - n_fft//2 = {self.n_fft - self.n_fft // 2}, "
+                             f"got {self.hop_length}")
+        self.reset()
+
+    def reset(self) -> None:
+        """Forget the stream: the next chunk starts a new one (any batch size)."""
+        self._carry = None                  # [in, out]: (B, n_fft - hop) partial sums, swapped after every call
+        self._B = None
+        self._one_d = None
+        self._device = None
+        self._flushed = False
+        self.frames_consumed = 0
+        self.samples_emitted = 0
+
+    # -- internals ---------------------------------------------------------------------------------
+    def _trim(self) -> int:
+        return self.n_fft // 2 if self.center else 0
+
+    def _run(self, S, T: int, final: bool) -> torch.Tensor:
+        n, hop, dev, B = self.n_fft, self.hop_length, self._device, self._B
+        frame0 = self.frames_consumed
+        K = frame0 + T
+        lo = max(frame0 * hop, self._trim())
+        hi = (K - 1) * hop + n - self._trim() if final else K * hop
+        hi = max(hi, lo)
+        out = torch.empty((B, hi - lo), dtype=torch.float32, device=dev)
+        if self._carry is None:
+            self._carry = [torch.empty((B, max(n - hop, 1)), dtype=torch.float32, device=dev) for _ in range(2)]
+        win = _get_padded_window(self.window, self.win_length, n, dev)
+        tw = _get_twiddles(n, dev)
+        if S is not None:
+            row_stride = _padded_row_stride(S)
+            n_ws = int(_x.lib().ap_istft_stream_workspace_floats(B, T, n, hop))
+            if row_stride is None or n_ws:
+                S = S.contiguous()
+                row_stride = T
+            ws = torch.empty(n_ws, dtype=torch.float32, device=dev) if n_ws else None
+            s_ptr = _x.ptr(torch.view_as_real(S))
+        else:
+            row_stride, ws, s_ptr = 0, None, None
+        _x.check(_x.dlib(dev).ap_istft_stream_f32(
+            s_ptr, B, T, row_stride, n, hop, _x.ptr(win), _x.ptr(tw), frame0, _x.ptr(self._carry[0]),
+            _x.ptr(self._carry[1]), int(final), lo, hi, None if ws is None else _x.ptr(ws), _x.ptr(out),
+            _x.stream_ptr(dev)))
+        self._carry.reverse()
+        self.frames_consumed = K
+        self.samples_emitted += hi - lo
+        return out[0] if self._one_d else out
+
+    def process(self, S_chunk) -> torch.Tensor:
+        """Feed the next frames (complex (F, T) or (B, F, T), dense or a strided view, on the device or the
+        host); returns the samples they finish, (n,) or (B, n)."""
+        if self._flushed:
+            raise ValueError("process() after flush(): call reset() to start a new stream")
+        S = S_chunk if isinstance(S_chunk, torch.Tensor) else torch.as_tensor(np.asarray(S_chunk))
+        if S.ndim not in (2, 3):
+            raise ValueError(f"S_chunk must be 2D or 3D, got {S.ndim}D")
+        one_d = S.ndim == 2
+        if one_d:
+            S = S[None]
+        B, F, T = S.shape
+        if F != self.n_fft // 2 + 1:
+            raise ValueError(f"S_chunk has {F} frequency bins but n_fft={self.n_fft} needs {self.n_fft // 2 + 1}")
+        if self._B is None:
+            self._B, self._one_d = B, one_d
+            self._device = S.device if S.is_cuda else _x.require_device()
+        elif B != self._B or one_d != self._one_d:
+            raise ValueError(f"every chunk must have the same batch layout: got {tuple(S_chunk.shape)} after "
+                             f"{'(F, T)' if self._one_d else f'({self._B}, F, T)'} chunks")
+        S = S.to(device=self._device, dtype=torch.complex64)
+        if T == 0:
+            e = torch.empty((B, 0), dtype=torch.float32, device=self._device)
+            return e[0] if one_d else e
+        return self._run(S, T, final=False)
+
+    def flush(self) -> torch.Tensor:
+        """End of stream: the last n_fft - hop samples (fewer with center=True), normalised with the envelope of
+        the frames actually fed.  The stream is finished afterwards (reset() starts a new one)."""
+        if self._flushed:
+            raise ValueError("flush() called twice: call reset() to start a new stream")
+        if self.frames_consumed == 0:
+            raise ValueError("flush() before any frame")
+        out = self._run(None, 0, final=True)
+        self._flushed = True
+        return out
