@@ -15,11 +15,13 @@
 //     contraction passes (NPASS), the hop class (HOPJ), (clip, frame) advanced incrementally
 //     instead of a 64-bit division per frame, part descriptors as ready-made LDS addresses, rows
 //     >= n_mels computed like the others and simply not stored, the window pairs and the split
-//     twiddles of the lane in registers for the whole kernel (46 VGPRs: 16 LDS reads and 14
+//     twiddles of the lane in registers for the whole kernel (48 VGPRs: 16 LDS reads and 14
 //     packed multiplies fewer per frame);
-//   * the quad radix-4 runs on v_fmac_f32_dpp: the DPP operand feeds the FMA directly
-//     (h += c * quad_perm(h)) and the two per-lane signs are folded into the W_64 twiddles that
-//     precede it - 64 DPP FMAs + 48 plain ops instead of 64 DPP moves + 64 packed ops;
+//   * the last radix-4 runs in registers, not across the quad: exchange #2 hands every lane four
+//     whole radix-4 groups that are also each other's mirrors (g and 256 - g), so the radix-4s and
+//     the paired real split take the lane's 16 bins without another LDS round trip - 32 packed adds
+//     and 8 selects instead of the 64 v_fmac_f32_dpp, 32 v_cndmask and the s_nop pads of the DPP
+//     quad stage (apm_quad8), and 8 ds_read_b128 instead of 17 ds_read_b64 for the split;
 //   * the 8-frame output run of a lane's two mel rows lives in registers (32 contiguous bytes per
 //     row and lane, as in ap_mel1024_wave_kernel): no output tile in LDS; the partial sums
 //     alias the idle upper half of the wave's exchange buffer.
@@ -35,23 +37,53 @@
 #define APM_RUN 8             // frames per output run held in registers
 #define APM_PARTIAL_OFF 1152  // float offset of the partial sums inside the wave's X buffer (plane: 1025 floats)
 
-// (ApmLane, apm_quad8 / apm_quad_radix4: kernels_wave.h - the STFT and irfft kernels use them too)
-
 // Which frame-invariant per-lane tables stay in REGISTERS for the whole kernel instead of being
 // re-read from LDS every frame (bit mask; 8 waves per CU leave 256 VGPRs per lane).  The product
 // uses APM_REGS: with the two twiddle tables as well hipcc's scheduler spills inside the frame loop.
 #define APM_REG_WIN 1         // window pairs                 32 VGPRs, saves 16 ds_read_b64 per frame
 #define APM_REG_TW1 2         // W_1024^(lane k1)             30 VGPRs, saves 15
-#define APM_REG_TW2 4         // (s1 s2) W_64^(a c)           30 VGPRs, saves 15
-#define APM_REG_SPLIT 8       // W_2048^(lane + 64 r) / 2     14 VGPRs, saves 14 packed multiplies
+#define APM_REG_TW2 4         // W_64^(a c)                   30 VGPRs, saves 15
+#define APM_REG_SPLIT 8       // W_2048^k / 2 of the 8 split pairs, 16 VGPRs (always in registers: apm_split;
+                              // the bit stays in APM_REGS so that the instantiations keep their names)
 #define APM_REGS (APM_REG_WIN | APM_REG_SPLIT)
 
-// forward transform of apw_forward with the fmac-DPP quad stage; tw2row holds sg * W_64^(a c)
+// Exchange #2 holds the second radix-16's outputs grouped by the last radix-4: the 4 inputs a of
+// group g = k1 + 16 c (outputs Z[g + 256 q]) are 32 contiguous bytes at complex slot apm_gidx(g), with
+// 16 bytes of padding after every 8 groups: the 16 ds_write_b64 of a frame are conflict-free and the
+// 8 ds_read_b128 take 48 bank cycles (ideal 32; tools/lds_banks.py).  Largest slot 1085 < APW_X_COMPLEX.
+AP_DEV int apm_gidx(int g) { return 4 * g + 2 * (g >> 3); }
+
+// Lane layout of the in-register radix-4 + split: the lane with index L takes the groups L, L + 64,
+// 192 - L, 256 - L (L = 0: 0, 64, 192, 128) - g pairs with 256 - g, as bin k = g + 256 q mirrors to
+// 1024 - k = (256 - g) + 256 (3 - q), so the split of all 16 bins happens in the lane's registers.
+// L is the lane permuted within its half: the four 16-lane sets of a ds_read_b128 ({0-3, 12-15, 20-27},
+// {4-11, 16-19, 28-31}, + 32) then read 16 consecutive groups each, which the padding above serves with
+// at most 2-way conflicts; every |X|^p store still covers 32 consecutive bins per half-wave.
+struct ApmPairLane {
+    int L, lp;           // the lane's index, and L or 128 (L = 0) for pairs 2 and 3
+    bool l0;             // L == 0: groups 0 and 128 pair with themselves, bin 512 on its own
+    int rd[4];           // exchange slots of the lane's four groups
+};
+
+AP_DEV ApmPairLane apm_pair_lane_init(int lane) {
+    ApmPairLane p;
+    p.L = (int)((0xE311825200ull >> (5 * ((lane >> 2) & 7))) & 31) + (lane & 3) + (lane & 32);  // 0,16,20,4,24,8,12,28
+    p.l0 = p.L == 0;
+    p.lp = p.l0 ? 128 : p.L;
+    p.rd[0] = apm_gidx(p.L);
+    p.rd[1] = apm_gidx(p.L + 64);
+    p.rd[2] = apm_gidx(192 - p.L);
+    p.rd[3] = apm_gidx(256 - p.lp);
+    return p;
+}
+
+// forward transform of apw_forward up to the W_64 twiddles; the last radix-4 is left to apm_split,
+// the exchange hands it whole groups.  tw2row holds plain W_64^(a c) rows (apw_fill_tables<false>).
 // (the samples x and the window pairs w go in separately: the window rides on the first butterfly level)
 template <int REGS>
 AP_DEV void apm_forward(const ap_float2 (&x)[16], const ap_float2 (&w)[16], ap_float2 *X, const ap_float2 *TW1,
                         const ap_float2 *tw2row, const ap_float2 (&t1r)[16], const ap_float2 (&t2r)[16],
-                        const ApwLane &c, const ApmLane &m) {
+                        const ApwLane &c) {
     const int lane = c.lane;
     ap_float2 v[16];
     if (REGS & APM_REG_TW1) {
@@ -81,39 +113,64 @@ AP_DEV void apm_forward(const ap_float2 (&x)[16], const ap_float2 (&w)[16], ap_f
     }
     AP_WAVE_SYNC();
     ApButterfly<16>::run(v);
-    v[0] = ap_scale(v[0], m.sg);
 #pragma unroll
     for (int cc = 1; cc < 16; ++cc) v[cc] = ap_mul_fw(v[cc], (REGS & APM_REG_TW2) ? t2r[cc] : t2[cc]);
-    apm_quad_radix4(v, m);
+    // exchange #2: v[cc] is input a = lane & 3 of group k1 + 16 cc (apm_gidx(k1 + 16 cc) = apm_gidx(k1) + 68 cc)
+    const int wb = apm_gidx(c.k1p) + (lane & 3);
 #pragma unroll
-    for (int cc = 0; cc < 16; ++cc) X[apw_zidx(c.k1p + 16 * cc + 256 * c.qd)] = v[cc];
+    for (int cc = 0; cc < 16; ++cc) X[wb + 68 * cc] = v[cc];
     AP_WAVE_SYNC();
 }
 
-// apw_split (kernels_wave.h) for |X| only, with the eight split twiddles W_2048^(lane + 64 r) / 2
-// optionally held in registers
-template <int REGS>
-AP_DEV void apm_split(const ap_float2 *X, const ApwLane &c, const ap_float2 (&wsp)[8], ap_float2 (&xk)[8],
-                      ap_float2 (&xm)[8], ap_float2 &zh) {
-    ap_float2 zk[8], zm[8];
+// The lane's four groups out of the exchange, their radix-4s (ap_fft4: the same additions, in the same
+// order, as the DPP quad stage of apw_forward) and the eight paired real splits of apw_split, all in
+// registers; |X|^p of the 16 bins (and bin 512 on lane L = 0) into the plane pp, which aliases X.
+// wsp[i]: W_2048^k / 2 of pair i (apm_split_twiddles).
+//   pair   0      1        2         3         4         5         6         7
+//   k      L      L + 256  512 - lp  256 - lp  L + 64    L + 320   448 - L   192 - L
+AP_DEV void apm_pair_bins(const ApmPairLane &p, int (&k)[8]) {
+    k[0] = p.L; k[1] = p.L + 256; k[2] = 512 - p.lp; k[3] = 256 - p.lp;
+    k[4] = p.L + 64; k[5] = p.L + 320; k[6] = 448 - p.L; k[7] = 192 - p.L;
+}
+
+AP_DEV void apm_split_twiddles(const ApmPairLane &p, const ap_float2 *tw, ap_float2 (&wsp)[8]) {
+    int k[8];
+    apm_pair_bins(p, k);
 #pragma unroll
-    for (int r = 0; r < 8; ++r) {
-        const int k = c.lane + 64 * r;
-        zk[r] = X[apw_zidx(k)];
-        zm[r] = X[apw_zidx((APW_NC - k) & (APW_NC - 1))];
+    for (int i = 0; i < 8; ++i) wsp[i] = ap_scale(tw[k[i]], 0.5f);
+}
+
+template <int PMODE>
+AP_DEV void apm_split(const ap_float2 *X, float *pp, const ApmPairLane &p, const ap_float2 (&wsp)[8],
+                      const ApwLane &c, float power) {
+    ap_float2 z[4][4];                    // z[s][q] = Z[g_s + 256 q] after the radix-4s
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        const ap_float4 *src = reinterpret_cast<const ap_float4 *>(X + p.rd[s]);
+        const ap_float4 lo = src[0], hi = src[1];
+        z[s][0] = ap_mk(lo.x, lo.y); z[s][1] = ap_mk(lo.z, lo.w);
+        z[s][2] = ap_mk(hi.x, hi.y); z[s][3] = ap_mk(hi.z, hi.w);
     }
-    zh = X[apw_zidx(APW_NC / 2)];
     AP_WAVE_SYNC();
 #pragma unroll
-    for (int r = 0; r < 8; ++r) {
-        const ap_float2 a = ap_add_conj(zk[r], zm[r]);
-        const ap_float2 d = ap_sub_conj(zk[r], zm[r]);
-        const ap_float2 w = (REGS & APM_REG_SPLIT) ? wsp[r]
-                                                   : (r == 0 ? c.tws0h : ap_mul_bw_c(c.tws0h, APW_C32(r), APW_S32(r)));
-        const ap_float2 u = ap_mul_fw(d, w);
-        xk[r] = ap_fma_add_mi(a, c.half, u);
-        xm[r] = ap_fma_sub_mi(a, c.half, u);
+    for (int s = 0; s < 4; ++s) ap_fft4(z[s][0], z[s][1], z[s][2], z[s][3]);
+    // (Z[k], Z[1024 - k]) of the eight pairs; L = 0: (Z0, Z0), (Z256, Z768), (Z384, Z640), (Z128, Z896)
+    const ap_float2 zk[8] = {z[0][0], z[0][1], z[3][1], z[3][0], z[1][0], z[1][1], z[2][1], z[2][0]};
+    const ap_float2 zm[8] = {p.l0 ? z[0][0] : z[3][3], p.l0 ? z[0][3] : z[3][2], p.l0 ? z[3][2] : z[0][2],
+                             p.l0 ? z[3][3] : z[0][3], z[2][3], z[2][2], z[1][2], z[1][3]};
+    int k[8];
+    apm_pair_bins(p, k);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const ap_float2 a = ap_add_conj(zk[i], zm[i]);
+        const ap_float2 d = ap_sub_conj(zk[i], zm[i]);
+        const ap_float2 u = ap_mul_fw(d, wsp[i]);
+        const ap_float2 xk = ap_fma_add_mi(a, c.half, u);
+        const ap_float2 xm = ap_fma_sub_mi(a, c.half, u);
+        pp[k[i]] = apw_pow2x<PMODE>(xk.x, xk.y, power);
+        pp[APW_NC - k[i]] = apw_pow2x<PMODE>(xm.x, xm.y, power);
     }
+    if (p.l0) pp[APW_NC / 2] = apw_pow2x<PMODE>(z[0][2].x, z[0][2].y, power);   // X[512] = conj Z[512]
 }
 
 #ifdef AP_DIAG_STAMPS
@@ -170,13 +227,12 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) ap_mel2048_run_kernel(ApMelWa
         const int nt = 64 * NW;
         ap_float4 *wq = reinterpret_cast<ap_float4 *>(ap_smem + P.off_wq);
         for (int i = tid; i < P.n_quads; i += nt) wq[i] = reinterpret_cast<const ap_float4 *>(P.quads)[i];
-        apw_fill_tables(TW2, reinterpret_cast<ap_float2 *>(ap_smem + P.off_tw1),
-                        reinterpret_cast<ap_float2 *>(ap_smem + P.off_win), P.tw, P.window, tid, nt);
+        apw_fill_tables<false>(TW2, reinterpret_cast<ap_float2 *>(ap_smem + P.off_tw1),
+                               reinterpret_cast<ap_float2 *>(ap_smem + P.off_win), P.tw, P.window, tid, nt);
     }
     AP_LDS_BARRIER();
-    // (apw_fill_tables has folded the quad stage's signs s1 s2 into the W_64 rows)
     const ApwLane lc = apw_lane_init(lane, TW2, P.tw);
-    const ApmLane lm = apm_lane_init(lane);
+    const ApmPairLane pl = apm_pair_lane_init(lane);
     // per-lane tables kept in registers (REGS): straight from the global tables
     ap_float2 winr[16], t1r[16], t2r[16], wsp[8];
 #pragma unroll
@@ -184,11 +240,9 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) ap_mel2048_run_kernel(ApMelWa
         winr[j] = (REGS & APM_REG_WIN) ? reinterpret_cast<const ap_float2 *>(P.window)[lane + 64 * j] : ap_mk(0.0f, 0.0f);
         if (IN16 == 1) winr[j] = ap_scale(winr[j], 1.0f / 32768.0f);      // 16-bit PCM -> [-1, 1): folded into the window
         t1r[j] = (REGS & APM_REG_TW1) ? P.tw[(2 * lane * j) & 2047] : ap_mk(0.0f, 0.0f);        // W_1024^(lane j)
-        t2r[j] = (REGS & APM_REG_TW2) ? ap_scale(P.tw[32 * (lane & 3) * j], lm.sg) : ap_mk(0.0f, 0.0f);
+        t2r[j] = (REGS & APM_REG_TW2) ? P.tw[32 * (lane & 3) * j] : ap_mk(0.0f, 0.0f);
     }
-#pragma unroll
-    for (int r = 0; r < 8; ++r)
-        wsp[r] = (REGS & APM_REG_SPLIT) ? ap_scale(P.tw[lane + 64 * r], 0.5f) : ap_mk(0.0f, 0.0f);
+    apm_split_twiddles(pl, P.tw, wsp);
     // frame-invariant contraction state: LDS addresses of this lane's entries
     const ap_float4 *pqa[NPASS], *pqb[NPASS];
     float *sa[NPASS], *sb[NPASS];
@@ -293,7 +347,7 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) ap_mel2048_run_kernel(ApMelWa
                     for (int j = 0; j < 16; ++j) ws[j] = WIN[lane + 64 * j];
                 }
                 AP_SCHED_FENCE();
-                apm_forward<REGS>(xs, ws, X, TW1, lc.tw2row, t1r, t2r, lc, lm);
+                apm_forward<REGS>(xs, ws, X, TW1, lc.tw2row, t1r, t2r, lc);
             }
             // The next frame of this wave's stretch, in flight during split + contraction
             AP_SCHED_FENCE();
@@ -321,17 +375,7 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) ap_mel2048_run_kernel(ApMelWa
                 }
             }
             AP_SCHED_FENCE();
-            {
-                ap_float2 xk[8], xm[8], zh;
-                apm_split<REGS>(X, lc, wsp, xk, xm, zh);
-#pragma unroll
-                for (int r = 0; r < 8; ++r) {
-                    const int k = lane + 64 * r;
-                    pp[k] = apw_pow2x<PMODE>(xk[r].x, xk[r].y, P.power);
-                    pp[APW_NC - k] = apw_pow2x<PMODE>(xm[r].x, xm[r].y, P.power);
-                }
-                if (lane == 0) pp[APW_NC / 2] = apw_pow2x<PMODE>(zh.x, zh.y, P.power);
-            }
+            apm_split<PMODE>(X, pp, pl, wsp, lc, P.power);
             AP_WAVE_SYNC();
             // ---- plan-based contraction: NPASS branch-free passes (kernels_wave.h) -------------
 #pragma unroll
@@ -473,22 +517,19 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) ap_spec2048_run_kernel(ApSpec
     const ap_float2 *TW1 = reinterpret_cast<const ap_float2 *>(ap_smem + P.off_tw1);
     const ap_float2 *WIN = reinterpret_cast<const ap_float2 *>(ap_smem + P.off_win);
     float *pp = reinterpret_cast<float *>(X);                 // |X|^p plane of this wave (floats 0..1024)
-    apw_fill_tables(TW2, reinterpret_cast<ap_float2 *>(ap_smem + P.off_tw1),
-                    reinterpret_cast<ap_float2 *>(ap_smem + P.off_win), P.tw, P.window, tid, 64 * NW);
+    apw_fill_tables<false>(TW2, reinterpret_cast<ap_float2 *>(ap_smem + P.off_tw1),
+                           reinterpret_cast<ap_float2 *>(ap_smem + P.off_win), P.tw, P.window, tid, 64 * NW);
     AP_LDS_BARRIER();
-    // (apw_fill_tables has folded the quad stage's signs s1 s2 into the W_64 rows)
     const ApwLane lc = apw_lane_init(lane, TW2, P.tw);
-    const ApmLane lm = apm_lane_init(lane);
+    const ApmPairLane pl = apm_pair_lane_init(lane);
     ap_float2 winr[16], t1r[16], t2r[16], wsp[8];
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
         winr[j] = (REGS & APM_REG_WIN) ? reinterpret_cast<const ap_float2 *>(P.window)[lane + 64 * j] : ap_mk(0.0f, 0.0f);
         t1r[j] = (REGS & APM_REG_TW1) ? P.tw[(2 * lane * j) & 2047] : ap_mk(0.0f, 0.0f);
-        t2r[j] = (REGS & APM_REG_TW2) ? ap_scale(P.tw[32 * (lane & 3) * j], lm.sg) : ap_mk(0.0f, 0.0f);
+        t2r[j] = (REGS & APM_REG_TW2) ? P.tw[32 * (lane & 3) * j] : ap_mk(0.0f, 0.0f);
     }
-#pragma unroll
-    for (int r = 0; r < 8; ++r)
-        wsp[r] = (REGS & APM_REG_SPLIT) ? ap_scale(P.tw[lane + 64 * r], 0.5f) : ap_mk(0.0f, 0.0f);
+    apm_split_twiddles(pl, P.tw, wsp);
     float fk[17];                                             // bin centres of this lane's bins
 #pragma unroll
     for (int i = 0; i < 16; ++i) fk[i] = P.freq[16 * lane + i];
@@ -533,7 +574,7 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) ap_spec2048_run_kernel(ApSpec
                 for (int j = 0; j < 16; ++j) ws[j] = WIN[lane + 64 * j];
             }
             AP_SCHED_FENCE();
-            apm_forward<REGS>(xs, ws, X, TW1, lc.tw2row, t1r, t2r, lc, lm);
+            apm_forward<REGS>(xs, ws, X, TW1, lc.tw2row, t1r, t2r, lc);
         }
         AP_SCHED_FENCE();
         if (more) {
@@ -549,17 +590,7 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) ap_spec2048_run_kernel(ApSpec
             }
         }
         AP_SCHED_FENCE();
-        {
-            ap_float2 xk[8], xm[8], zh;
-            apm_split<REGS>(X, lc, wsp, xk, xm, zh);
-#pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                const int k = lane + 64 * r;
-                pp[k] = apw_pow2x<PMODE>(xk[r].x, xk[r].y, P.power);
-                pp[APW_NC - k] = apw_pow2x<PMODE>(xm[r].x, xm[r].y, P.power);
-            }
-            if (lane == 0) pp[APW_NC / 2] = apw_pow2x<PMODE>(zh.x, zh.y, P.power);
-        }
+        apm_split<PMODE>(X, pp, pl, wsp, lc, P.power);
         AP_WAVE_SYNC();
         // ---- this lane's 16 (17) contiguous bins -------------------------------------------
         float v[17];

@@ -188,12 +188,14 @@ AP_DEV ApwLane apw_lane_init(int lane, const ap_float2 *TW2, const ap_float2 *tw
 }
 
 // workgroup tables: W_64^(a*c) [4][17], W_1024^(lane*k1) [16][64], window as 1024 float pairs
+// (QUAD_SIGNS = false: plain W_64 rows, for kernels whose last radix-4 runs in registers)
+template <bool QUAD_SIGNS = true>
 AP_DEV void apw_fill_tables(ap_float2 *tw2, ap_float2 *tw1, ap_float2 *win, const ap_float2 *tw,
                             const float *window, int tid, int nt) {
     // W_64^(a c) with the quad stage's per-lane signs s1 s2 of row a folded in (apm_quad8 works on (s1 s2) v)
     if (tid < 64) {
         const int a = tid >> 4;
-        tw2[a * 17 + (tid & 15)] = ap_scale(tw[32 * a * (tid & 15)], (a == 1 || a == 2) ? -1.0f : 1.0f);
+        tw2[a * 17 + (tid & 15)] = ap_scale(tw[32 * a * (tid & 15)], (QUAD_SIGNS && (a == 1 || a == 2)) ? -1.0f : 1.0f);
     }
     for (int i = tid; i < 16 * 64; i += nt) tw1[i] = tw[2 * (i & 63) * (i >> 6)];
     for (int i = tid; i < APW_NC; i += nt) win[i] = reinterpret_cast<const ap_float2 *>(window)[i];
