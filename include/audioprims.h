@@ -529,6 +529,25 @@ int ap_acf_peaks_f32(const float *r /*dev*/, int64_t rows, int n_lag, int min_la
                      float threshold, float sr, float *f0 /*dev (rows)*/,
                      unsigned char *voiced /*dev (rows)*/, float *periodicity /*dev (rows)*/, void *stream);
 
+/* yin / yin_cmnd (pitch.py; de Cheveigne & Kawahara 2002).  Frames of frame_length = n (even, 4 .. 8192) every
+ * `hop` samples, T = ap_n_frames of stft (center: n / 2 zeros on both sides); with W = n / 2 and the lags
+ * 1 <= lo < hi <= n - W - 1:
+ *   d(tau) = sum_{j<W} (x[j] - x[j + tau])^2,  d'(0) = 1,  d'(tau) = d(tau) tau / sum_{k=1..tau} d(k)
+ *   (1 where that sum is 0; no absolute floor: d' is invariant under scaling of y).
+ * ap_yin_cmnd_f32 stores d'(lo .. hi) as out (B, hi - lo + 1, T).  ap_yin_f32 picks on that curve the first lag
+ * with d' < trough_threshold that is below its left and not above its right neighbour (values outside the curve
+ * count as +inf), else the first global minimum; interior picks are refined by the parabola through the three
+ * values; f0 = sr / lag (B, T), aper (optional) = d' at the picked integer lag.
+ * tw selects the kernel: the twiddle table of ap_twiddle_table_host(n) asks for the fused wave-per-frame kernel
+ * (three on-chip n-point transforms per frame; AP_ERR_UNSUPPORTED when ap_yin_fused(n, hop, L) == 0, i.e. unless
+ * n = 2048 or 1024, hop even, L <= 2^28); NULL runs the general kernel (one workgroup per frame, direct sums, any n). */
+int ap_yin_fused(int frame_length, int hop, int64_t L);
+int ap_yin_f32(const float *y /*dev (B,L)*/, int64_t B, int64_t L, int frame_length, int hop, int center, int lo,
+               int hi, float sr, float trough_threshold, const float *tw /*dev or NULL*/, float *f0 /*dev (B,T)*/,
+               float *aper /*dev (B,T) or NULL*/, void *stream);
+int ap_yin_cmnd_f32(const float *y /*dev (B,L)*/, int64_t B, int64_t L, int frame_length, int hop, int center,
+                    int lo, int hi, const float *tw /*dev or NULL*/, float *out /*dev (B,hi-lo+1,T)*/, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

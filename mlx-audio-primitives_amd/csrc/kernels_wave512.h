@@ -558,7 +558,7 @@ struct ApIstftWave512Params {
     int off_tw1, off_tw2, off_win, off_ib, off_carry, lds_bytes;
 };
 
-__global__ void __launch_bounds__(64 * APHS_WAVES, 4) ap_istft1024_wave_kernel(ApIstftWave512Params P) {
+AP_KERNEL void __launch_bounds__(64 * APHS_WAVES, 4) ap_istft1024_wave_kernel(ApIstftWave512Params P) {
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = AP_UNIFORM(tid >> 6);
