@@ -925,3 +925,179 @@ static inline int ap_prepare_irfft(ApIrfftParams &P, const float *S, int64_t B, 
     if (P.tiles_per_clip * B > kApMaxGrid) AP_FAIL(AP_ERR_UNSUPPORTED, "irfft: grid too large");
     return AP_OK;
 }
+
+// ---------------------------------------------------------------------- features / framing (kernels_features.h)
+// The parameter blocks and tile constants live beside the kernels; the prepare functions take the block as a
+// template argument and the constants (APF_TX, APF_MAX_BLOCKS, APD_PER, APSG_PER) from the call site.
+// *grid == 0 on AP_OK: nothing was asked for, nothing to launch.
+template <class SP>
+static inline int ap_prepare_spectral_stats(SP &P, const float *S, int is_complex, int64_t B, int64_t F, int64_t T,
+                                            const float *freq, float power, const float *centroid_in, float p, int norm,
+                                            float roll_percent, float amin, float *centroid, float *bandwidth,
+                                            float *rolloff, float *flatness, int tx, int64_t *grid) {
+    *grid = 0;
+    if (!S || !freq) AP_FAIL(AP_ERR_INVALID, "spectral features: NULL buffer");
+    if (B <= 0 || F <= 0 || T <= 0)
+        AP_FAIL(AP_ERR_INVALID, "S must be 2D (freq_bins, n_frames) or 3D (batch, freq_bins, n_frames)");
+    if (roll_percent < 0.0f || roll_percent > 1.0f) AP_FAIL(AP_ERR_INVALID, "roll_percent must be between 0 and 1");
+    if (!(p > 0.0f)) AP_FAIL(AP_ERR_INVALID, "p must be positive");
+    if (!centroid && !bandwidth && !rolloff && !flatness) return AP_OK;
+    P.S = S; P.freq = freq; P.centroid_in = centroid_in;
+    P.centroid = centroid; P.bandwidth = bandwidth; P.rolloff = rolloff; P.flatness = flatness;
+    P.F = F; P.T = T; P.tiles_per_clip = (T + tx - 1) / tx;
+    P.is_complex = is_complex; P.norm = norm;
+    P.power = power; P.p = p; P.roll_percent = roll_percent; P.amin = amin;
+    if (P.tiles_per_clip * B > kApMaxGrid) AP_FAIL(AP_ERR_UNSUPPORTED, "spectral features: grid too large");
+    *grid = P.tiles_per_clip * B;
+    return AP_OK;
+}
+
+// RMS / ZCR.  *route: 0 = nothing to do, AP_FRAME_ROUTE_BLOCKS (Q filled: frame_length = m hop, every sample read
+// once) or AP_FRAME_ROUTE_SPAN (P and *lds filled: the contiguous span of G frames staged in dynamic LDS).
+// `allow_blocks` = 0 keeps the span kernel (the A/B switch of the caller); the block route halves its tile until
+// `fill_grid` workgroups exist (the chip-filling heuristic; 0 keeps the full tile of max_blocks slots).
+#define AP_FRAME_ROUTE_BLOCKS 1
+#define AP_FRAME_ROUTE_SPAN 2
+template <class QB, class PS>
+static inline int ap_prepare_frame_stats(QB &Q, PS &P, const float *y, int64_t B, int64_t L, int frame_length, int hop,
+                                         int center, int pad_mode, int64_t T, float *rms, float *zcr, int max_blocks,
+                                         int allow_blocks, int64_t fill_grid, int *route, int64_t *grid, int *lds) {
+    *route = 0;
+    *grid = 0;
+    *lds = 0;
+    if (!y) AP_FAIL(AP_ERR_INVALID, "frame statistics: NULL buffer");
+    if (frame_length <= 0) AP_FAIL(AP_ERR_INVALID, "frame_length must be positive, got %d", frame_length);
+    if (hop <= 0) AP_FAIL(AP_ERR_INVALID, "hop_length must be positive, got %d", hop);
+    if (pad_mode != AP_PAD_CONSTANT && pad_mode != AP_PAD_EDGE)
+        AP_FAIL(AP_ERR_INVALID, "Unknown pad_mode. Supported: 'constant', 'edge'");
+    if (B <= 0 || L <= 0) AP_FAIL(AP_ERR_INVALID, "frame statistics: signal must be non-empty");
+    const int pad = center ? frame_length / 2 : 0;
+    const int64_t Lp = L + 2 * (int64_t)pad;
+    if (Lp < frame_length)
+        AP_FAIL(AP_ERR_INVALID, "Signal length (%lld) must be >= frame_length (%d). Consider padding the signal.",
+                (long long)Lp, frame_length);
+    if (T != 1 + (Lp - frame_length) / hop)
+        AP_FAIL(AP_ERR_INVALID, "frame statistics: n_frames mismatch (got %lld)", (long long)T);
+    if (!rms && !zcr) return AP_OK;
+    // frames per workgroup: the contiguous span (G - 1) hop + frame_length has to fit 64 KiB of LDS
+    // frame_length = m hop: every sample read once (block partial sums)
+    if (hop % 4 == 0 && frame_length % hop == 0 && frame_length / hop <= 16 && allow_blocks) {
+        Q.y = y; Q.rms = rms; Q.zcr = zcr; Q.L = L; Q.T = T;
+        Q.frame_length = frame_length; Q.hop = hop; Q.pad = pad; Q.pad_mode = pad_mode;
+        Q.m = frame_length / hop;
+        int64_t G = max_blocks - Q.m + 1;
+        if (G > T) G = T;
+        // enough workgroups to fill the chip when the batch is small
+        while (G > 16 && ((T + G - 1) / G) * B < fill_grid) G = (G + 1) / 2;
+        Q.G = (int)G;
+        Q.tiles_per_clip = (T + G - 1) / G;
+        if (Q.tiles_per_clip * B <= kApMaxGrid) {
+            *route = AP_FRAME_ROUTE_BLOCKS;
+            *grid = Q.tiles_per_clip * B;
+            return AP_OK;
+        }
+    }
+    const int64_t budget = 16 * 1024;
+    if (frame_length > 36 * 1024) AP_FAIL(AP_ERR_UNSUPPORTED, "frame_length %d does not fit LDS", frame_length);
+    int64_t G = frame_length >= budget ? 1 : (budget - frame_length) / hop + 1;
+    if (G > 64) G = 64;
+    if (G > T) G = T;
+    P.y = y; P.rms = rms; P.zcr = zcr; P.L = L; P.T = T;
+    P.frame_length = frame_length; P.hop = hop; P.pad = pad; P.pad_mode = pad_mode; P.G = (int)G;
+    P.tiles_per_clip = (T + G - 1) / G;
+    if (P.tiles_per_clip * B > kApMaxGrid) AP_FAIL(AP_ERR_UNSUPPORTED, "frame statistics: grid too large");
+    *lds = (int)(((G - 1) * hop + frame_length) * sizeof(float));
+    *route = AP_FRAME_ROUTE_SPAN;
+    *grid = P.tiles_per_clip * B;
+    return AP_OK;
+}
+
+// *quads != 0: the four-samples-per-thread kernel (L % 4 == 0 and both buffers 16-byte aligned)
+static inline int ap_prepare_preemphasis(const float *y, int64_t B, int64_t L, float coef, const float *out, int *quads,
+                                         int *grid) {
+    if (!y || !out) AP_FAIL(AP_ERR_INVALID, "preemphasis: NULL buffer");
+    if (!(coef >= 0.0f && coef <= 1.0f)) AP_FAIL(AP_ERR_INVALID, "coef must be in [0, 1], got %g", (double)coef);
+    if (B <= 0 || L <= 0) AP_FAIL(AP_ERR_INVALID, "preemphasis: signal must be non-empty");
+    *quads = (L % 4 == 0 && ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(out)) & 15) == 0) ? 1 : 0;
+    *grid = ap_grid_1d(*quads ? B * L / 4 : B * L, AP_BLOCK, kApStreamGrid);
+    return AP_OK;
+}
+
+// De-emphasis: chunks of 4 tiles (`tile` = AP_BLOCK * APD_PER samples).  *chunked != 0: B * n_chunks workgroups,
+// end states into `ws` and then the chunks; else one workgroup per clip.
+static inline int64_t ap_deemphasis_chunk(int64_t tile) { return 4 * tile; }             // 16 384 samples
+static inline int ap_prepare_deemphasis(const float *y, int64_t B, int64_t L, float coef, const float *out,
+                                        const float *ws, int64_t tile, int64_t *chunk, int64_t *n_chunks, int *chunked) {
+    if (!y || !out) AP_FAIL(AP_ERR_INVALID, "deemphasis: NULL buffer");
+    if (!(coef >= 0.0f && coef <= 1.0f)) AP_FAIL(AP_ERR_INVALID, "coef must be in [0, 1], got %g", (double)coef);
+    if (B <= 0 || L <= 0) AP_FAIL(AP_ERR_INVALID, "deemphasis: signal must be non-empty");
+    *chunk = ap_deemphasis_chunk(tile);
+    *n_chunks = (L + *chunk - 1) / *chunk;
+    *chunked = (ws && *n_chunks > 1 && B * *n_chunks <= kApMaxGrid) ? 1 : 0;
+    if (!*chunked && B > kApMaxGrid) AP_FAIL(AP_ERR_UNSUPPORTED, "deemphasis: grid too large");
+    return AP_OK;
+}
+
+// Savitzky-Golay.  *chunks > 0: the rows kernel (contiguous axis, taps in LDS), outer * chunks workgroups of
+// `per_group` positions; *chunks == 0: the generic kernel on *grid workgroups.
+static inline int ap_prepare_savgol(const float *x, int64_t outer, int64_t n, int64_t inner, const float *taps, int width,
+                                    int mode, const float *edge, const float *out, int per_group, int64_t *chunks,
+                                    int64_t *grid) {
+    if (!x || !taps || !out) AP_FAIL(AP_ERR_INVALID, "delta: NULL buffer");
+    if (width < 3) AP_FAIL(AP_ERR_INVALID, "width must be >= 3, got %d", width);
+    if (width % 2 == 0) AP_FAIL(AP_ERR_INVALID, "width must be odd, got %d", width);
+    if (mode < AP_SG_INTERP || mode > AP_SG_WRAP) AP_FAIL(AP_ERR_INVALID, "delta: unknown mode");
+    if (outer <= 0 || n <= 0 || inner <= 0) AP_FAIL(AP_ERR_INVALID, "delta: empty array");
+    if (mode == AP_SG_INTERP && (!edge || width > n))
+        AP_FAIL(AP_ERR_INVALID, "when mode='interp', width=%d cannot exceed data.shape[axis]=%lld", width, (long long)n);
+    *chunks = 0;
+    if (inner == 1 && width <= 64 && n < (1 << 30)) {       // contiguous axis: one row chunk per workgroup
+        const int64_t c = (n + per_group - 1) / per_group;
+        if (outer * c <= kApMaxGrid) {
+            *chunks = c;
+            *grid = outer * c;
+            return AP_OK;
+        }
+    }
+    *grid = ap_grid_1d(outer * n * inner, AP_BLOCK, kApStreamGrid);
+    return AP_OK;
+}
+
+static inline int ap_prepare_extend(const float *x, int64_t B, int64_t L, int64_t n_ext, int mode, const float *out,
+                                    int *grid) {
+    if (!x || !out) AP_FAIL(AP_ERR_INVALID, "extend: NULL buffer");
+    if (B <= 0 || L <= 0 || n_ext < 0) AP_FAIL(AP_ERR_INVALID, "extend: signal must be non-empty");
+    if (mode < AP_EXT_CONSTANT || mode > AP_EXT_LINE) AP_FAIL(AP_ERR_INVALID, "extend: unknown mode %d", mode);
+    if (L < 2 && (mode == AP_EXT_SMOOTH || mode == AP_EXT_REFLECT || mode == AP_EXT_ANTIREFLECT || mode == AP_EXT_LINE))
+        AP_FAIL(AP_ERR_INVALID, "extend: this mode needs at least two samples");
+    *grid = ap_grid_1d(B * (L + 2 * n_ext), AP_BLOCK, kApStreamGrid);
+    return AP_OK;
+}
+
+// one thread per (clip, frame), one grid row per band
+static inline int ap_prepare_spectral_contrast(const float *S, int64_t B, int64_t F, int64_t T, const int32_t *bands,
+                                               int n_bands, const float *out, int64_t *blocks) {
+    if (!S || !bands || !out) AP_FAIL(AP_ERR_INVALID, "spectral_contrast: NULL buffer");
+    if (B <= 0 || F <= 0 || T <= 0)
+        AP_FAIL(AP_ERR_INVALID, "S must be 2D (freq_bins, n_frames) or 3D (batch, freq_bins, n_frames)");
+    if (n_bands <= 0 || n_bands > 65535) AP_FAIL(AP_ERR_INVALID, "n_bands must be positive");
+    *blocks = (B * T + AP_BLOCK - 1) / AP_BLOCK;
+    if (*blocks > kApMaxGrid) AP_FAIL(AP_ERR_UNSUPPORTED, "spectral_contrast: grid too large");
+    return AP_OK;
+}
+
+static inline int ap_prepare_acf_peaks(const float *r, int64_t rows, int n_lag, int min_lag, int64_t *grid) {
+    if (!r) AP_FAIL(AP_ERR_INVALID, "pitch: NULL buffer");
+    if (rows <= 0 || n_lag <= 0) AP_FAIL(AP_ERR_INVALID, "pitch: empty autocorrelation");
+    if (min_lag < 0) AP_FAIL(AP_ERR_INVALID, "pitch: negative lag");
+    *grid = (rows + AP_BLOCK - 1) / AP_BLOCK;
+    return AP_OK;
+}
+
+static inline int ap_prepare_pcm16(const int16_t *x, int64_t n, const float *out, int *grid) {
+    *grid = 0;
+    if (n < 0 || (n > 0 && (!x || !out))) AP_FAIL(AP_ERR_INVALID, "pcm16_to_f32: bad buffer");
+    if (n == 0) return AP_OK;
+    *grid = ap_grid_1d((n + 7) / 8, AP_BLOCK, kApStreamGrid);
+    return AP_OK;
+}

@@ -655,13 +655,10 @@ int ap_resample_poly_f32(const float *x, int64_t B, int64_t L, int up, int down,
 }
 
 int ap_extend_f32(const float *x, int64_t B, int64_t L, int64_t n_ext, int mode, float *out, void *stream) {
-    if (!x || !out) AP_FAIL(AP_ERR_INVALID, "extend: NULL buffer");
-    if (B <= 0 || L <= 0 || n_ext < 0) AP_FAIL(AP_ERR_INVALID, "extend: signal must be non-empty");
-    if (mode < AP_EXT_CONSTANT || mode > AP_EXT_LINE) AP_FAIL(AP_ERR_INVALID, "extend: unknown mode %d", mode);
-    if (L < 2 && (mode == AP_EXT_SMOOTH || mode == AP_EXT_REFLECT || mode == AP_EXT_ANTIREFLECT || mode == AP_EXT_LINE))
-        AP_FAIL(AP_ERR_INVALID, "extend: this mode needs at least two samples");
-    hipLaunchKernelGGL(ap_extend_kernel, dim3(ap_grid_1d(B * (L + 2 * n_ext), AP_BLOCK, kApStreamGrid)), dim3(AP_BLOCK), 0,
-                       (hipStream_t)stream, x, B, L, n_ext, mode, out);
+    int grid = 0;
+    int rc = ap_prepare_extend(x, B, L, n_ext, mode, out, &grid);
+    if (rc != AP_OK) return rc;
+    hipLaunchKernelGGL(ap_extend_kernel, dim3(grid), dim3(AP_BLOCK), 0, (hipStream_t)stream, x, B, L, n_ext, mode, out);
     return ap_check_launch("ap_extend_f32");
 }
 
@@ -1113,21 +1110,12 @@ int ap_complex_unary_rows_f32(const float *S, int64_t rows, int64_t T, int64_t r
 int ap_spectral_stats_f32(const float *S, int is_complex, int64_t B, int64_t F, int64_t T, const float *freq,
                           float power, const float *centroid_in, float p, int norm, float roll_percent, float amin,
                           float *centroid, float *bandwidth, float *rolloff, float *flatness, void *stream) {
-    if (!S || !freq) AP_FAIL(AP_ERR_INVALID, "spectral features: NULL buffer");
-    if (B <= 0 || F <= 0 || T <= 0)
-        AP_FAIL(AP_ERR_INVALID, "S must be 2D (freq_bins, n_frames) or 3D (batch, freq_bins, n_frames)");
-    if (roll_percent < 0.0f || roll_percent > 1.0f) AP_FAIL(AP_ERR_INVALID, "roll_percent must be between 0 and 1");
-    if (!(p > 0.0f)) AP_FAIL(AP_ERR_INVALID, "p must be positive");
-    if (!centroid && !bandwidth && !rolloff && !flatness) return AP_OK;
     ApSpectralParams P;
-    P.S = S; P.freq = freq; P.centroid_in = centroid_in;
-    P.centroid = centroid; P.bandwidth = bandwidth; P.rolloff = rolloff; P.flatness = flatness;
-    P.F = F; P.T = T; P.tiles_per_clip = (T + APF_TX - 1) / APF_TX;
-    P.is_complex = is_complex; P.norm = norm;
-    P.power = power; P.p = p; P.roll_percent = roll_percent; P.amin = amin;
-    if (P.tiles_per_clip * B > kApMaxGrid) AP_FAIL(AP_ERR_UNSUPPORTED, "spectral features: grid too large");
-    hipLaunchKernelGGL(ap_spectral_stats_kernel, dim3((unsigned)(P.tiles_per_clip * B)), dim3(APF_TX * APF_TY), 0,
-                       (hipStream_t)stream, P);
+    int64_t grid = 0;
+    int rc = ap_prepare_spectral_stats(P, S, is_complex, B, F, T, freq, power, centroid_in, p, norm, roll_percent, amin,
+                                       centroid, bandwidth, rolloff, flatness, APF_TX, &grid);
+    if (rc != AP_OK || grid == 0) return rc;
+    hipLaunchKernelGGL(ap_spectral_stats_kernel, dim3((unsigned)grid), dim3(APF_TX * APF_TY), 0, (hipStream_t)stream, P);
     return ap_check_launch("ap_spectral_stats_f32");
 }
 
@@ -1170,75 +1158,40 @@ int ap_spectral_audio_f32(const float *y, int64_t B, int64_t L, int n_fft, int h
 
 int ap_frame_stats_f32(const float *y, int64_t B, int64_t L, int frame_length, int hop, int center, int pad_mode,
                        int64_t T, float *rms, float *zcr, void *stream) {
-    if (!y) AP_FAIL(AP_ERR_INVALID, "frame statistics: NULL buffer");
-    if (frame_length <= 0) AP_FAIL(AP_ERR_INVALID, "frame_length must be positive, got %d", frame_length);
-    if (hop <= 0) AP_FAIL(AP_ERR_INVALID, "hop_length must be positive, got %d", hop);
-    if (pad_mode != AP_PAD_CONSTANT && pad_mode != AP_PAD_EDGE)
-        AP_FAIL(AP_ERR_INVALID, "Unknown pad_mode. Supported: 'constant', 'edge'");
-    if (B <= 0 || L <= 0) AP_FAIL(AP_ERR_INVALID, "frame statistics: signal must be non-empty");
-    const int pad = center ? frame_length / 2 : 0;
-    const int64_t Lp = L + 2 * (int64_t)pad;
-    if (Lp < frame_length)
-        AP_FAIL(AP_ERR_INVALID, "Signal length (%lld) must be >= frame_length (%d). Consider padding the signal.",
-                (long long)Lp, frame_length);
-    if (T != 1 + (Lp - frame_length) / hop)
-        AP_FAIL(AP_ERR_INVALID, "frame statistics: n_frames mismatch (got %lld)", (long long)T);
-    if (!rms && !zcr) return AP_OK;
-    // frames per workgroup: the contiguous span (G - 1) hop + frame_length has to fit 64 KiB of LDS
-    // frame_length = m hop: every sample read once (block partial sums)
-    if (hop % 4 == 0 && frame_length % hop == 0 && frame_length / hop <= 16 && !std::getenv("AP_FRAME_STATS_SPAN")) {
-        ApFrameBlocksParams Q;
-        Q.y = y; Q.rms = rms; Q.zcr = zcr; Q.L = L; Q.T = T;
-        Q.frame_length = frame_length; Q.hop = hop; Q.pad = pad; Q.pad_mode = pad_mode;
-        Q.m = frame_length / hop;
-        int64_t G = APF_MAX_BLOCKS - Q.m + 1;
-        if (G > T) G = T;
-        // enough workgroups to fill the chip when the batch is small
-        while (G > 16 && ((T + G - 1) / G) * B < 1024) G = (G + 1) / 2;
-        Q.G = (int)G;
-        Q.tiles_per_clip = (T + G - 1) / G;
-        if (Q.tiles_per_clip * B <= kApMaxGrid) {
-            hipLaunchKernelGGL(ap_frame_stats_blocks_kernel, dim3((unsigned)(Q.tiles_per_clip * B)), dim3(AP_BLOCK), 0,
-                               (hipStream_t)stream, Q);
-            return ap_check_launch("ap_frame_stats_f32(blocks)");
-        }
-    }
-    const int64_t budget = 16 * 1024;
-    if (frame_length > 36 * 1024) AP_FAIL(AP_ERR_UNSUPPORTED, "frame_length %d does not fit LDS", frame_length);
-    int64_t G = frame_length >= budget ? 1 : (budget - frame_length) / hop + 1;
-    if (G > 64) G = 64;
-    if (G > T) G = T;
+    ApFrameBlocksParams Q;
     ApFrameStatsParams P;
-    P.y = y; P.rms = rms; P.zcr = zcr; P.L = L; P.T = T;
-    P.frame_length = frame_length; P.hop = hop; P.pad = pad; P.pad_mode = pad_mode; P.G = (int)G;
-    P.tiles_per_clip = (T + G - 1) / G;
-    if (P.tiles_per_clip * B > kApMaxGrid) AP_FAIL(AP_ERR_UNSUPPORTED, "frame statistics: grid too large");
-    const int lds = (int)(((G - 1) * hop + frame_length) * sizeof(float));
-    int rc = ap_allow_lds(ap_frame_stats_kernel, lds);
+    int route = 0, lds = 0;
+    int64_t grid = 0;
+    int rc = ap_prepare_frame_stats(Q, P, y, B, L, frame_length, hop, center, pad_mode, T, rms, zcr, APF_MAX_BLOCKS,
+                                    std::getenv("AP_FRAME_STATS_SPAN") ? 0 : 1, 1024, &route, &grid, &lds);
+    if (rc != AP_OK || route == 0) return rc;
+    if (route == AP_FRAME_ROUTE_BLOCKS) {
+        hipLaunchKernelGGL(ap_frame_stats_blocks_kernel, dim3((unsigned)grid), dim3(AP_BLOCK), 0, (hipStream_t)stream, Q);
+        return ap_check_launch("ap_frame_stats_f32(blocks)");
+    }
+    rc = ap_allow_lds(ap_frame_stats_kernel, lds);
     if (rc != AP_OK) return rc;
-    hipLaunchKernelGGL(ap_frame_stats_kernel, dim3((unsigned)(P.tiles_per_clip * B)), dim3(AP_BLOCK), lds,
-                       (hipStream_t)stream, P);
+    hipLaunchKernelGGL(ap_frame_stats_kernel, dim3((unsigned)grid), dim3(AP_BLOCK), lds, (hipStream_t)stream, P);
     return ap_check_launch("ap_frame_stats_f32");
 }
 
 int ap_preemphasis_f32(const float *y, int64_t B, int64_t L, float coef, const float *zi, float *out, float *zf,
                        void *stream) {
-    if (!y || !out) AP_FAIL(AP_ERR_INVALID, "preemphasis: NULL buffer");
-    if (!(coef >= 0.0f && coef <= 1.0f)) AP_FAIL(AP_ERR_INVALID, "coef must be in [0, 1], got %g", (double)coef);
-    if (B <= 0 || L <= 0) AP_FAIL(AP_ERR_INVALID, "preemphasis: signal must be non-empty");
-    if (L % 4 == 0 && ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(out)) & 15) == 0)
-        hipLaunchKernelGGL(ap_preemphasis4_kernel, dim3(ap_grid_1d(B * L / 4, AP_BLOCK, kApStreamGrid)), dim3(AP_BLOCK), 0,
-                           (hipStream_t)stream, y, B, L, coef, zi, out, zf);
+    int quads = 0, grid = 0;
+    int rc = ap_prepare_preemphasis(y, B, L, coef, out, &quads, &grid);
+    if (rc != AP_OK) return rc;
+    if (quads)
+        hipLaunchKernelGGL(ap_preemphasis4_kernel, dim3(grid), dim3(AP_BLOCK), 0, (hipStream_t)stream, y, B, L, coef, zi,
+                           out, zf);
     else
-        hipLaunchKernelGGL(ap_preemphasis_kernel, dim3(ap_grid_1d(B * L, AP_BLOCK, kApStreamGrid)), dim3(AP_BLOCK), 0,
-                           (hipStream_t)stream, y, B, L, coef, zi, out, zf);
+        hipLaunchKernelGGL(ap_preemphasis_kernel, dim3(grid), dim3(AP_BLOCK), 0, (hipStream_t)stream, y, B, L, coef, zi,
+                           out, zf);
     return ap_check_launch("ap_preemphasis_f32");
 }
 
 int64_t ap_deemphasis_workspace_floats(int64_t B, int64_t L) {
     if (B <= 0 || L <= 0) return 0;
-    const int64_t tile = AP_BLOCK * APD_PER;
-    int64_t chunk = 4 * tile;                              // 16 384 samples
+    const int64_t chunk = ap_deemphasis_chunk((int64_t)AP_BLOCK * APD_PER);
     const int64_t n_chunks = (L + chunk - 1) / chunk;
     return n_chunks > 1 ? B * n_chunks : 0;
 }
@@ -1250,22 +1203,20 @@ int ap_deemphasis_f32(const float *y, int64_t B, int64_t L, float coef, const fl
 
 int ap_deemphasis_ws_f32(const float *y, int64_t B, int64_t L, float coef, const float *zi, float *out, float *zf,
                          float *ws, void *stream) {
-    if (!y || !out) AP_FAIL(AP_ERR_INVALID, "deemphasis: NULL buffer");
-    if (!(coef >= 0.0f && coef <= 1.0f)) AP_FAIL(AP_ERR_INVALID, "coef must be in [0, 1], got %g", (double)coef);
-    if (B <= 0 || L <= 0) AP_FAIL(AP_ERR_INVALID, "deemphasis: signal must be non-empty");
-    const int64_t chunk = 4 * (int64_t)AP_BLOCK * APD_PER;
-    const int64_t n_chunks = (L + chunk - 1) / chunk;
-    if (ws && n_chunks > 1 && B * n_chunks <= kApMaxGrid) {
+    int64_t chunk = 0, n_chunks = 0;
+    int chunked = 0;
+    int rc = ap_prepare_deemphasis(y, B, L, coef, out, ws, (int64_t)AP_BLOCK * APD_PER, &chunk, &n_chunks, &chunked);
+    if (rc != AP_OK) return rc;
+    if (chunked) {
         // chunked: end states of all chunks, then every chunk from its composed entering state
         hipLaunchKernelGGL(ap_deemphasis_kernel<1>, dim3((unsigned)(B * n_chunks)), dim3(AP_BLOCK), 0, (hipStream_t)stream,
                            y, L, coef, zi, zi ? 0 : 1, out, zf, chunk, (int)n_chunks, ws);
-        int rc = ap_check_launch("ap_deemphasis_f32(carries)");
+        rc = ap_check_launch("ap_deemphasis_f32(carries)");
         if (rc != AP_OK) return rc;
         hipLaunchKernelGGL(ap_deemphasis_kernel<2>, dim3((unsigned)(B * n_chunks)), dim3(AP_BLOCK), 0, (hipStream_t)stream,
                            y, L, coef, zi, zi ? 0 : 1, out, zf, chunk, (int)n_chunks, ws);
         return ap_check_launch("ap_deemphasis_f32(chunks)");
     }
-    if (B > kApMaxGrid) AP_FAIL(AP_ERR_UNSUPPORTED, "deemphasis: grid too large");
     hipLaunchKernelGGL(ap_deemphasis_kernel<0>, dim3((unsigned)B), dim3(AP_BLOCK), 0, (hipStream_t)stream, y, L, coef, zi,
                        zi ? 0 : 1, out, zf, L, 1, nullptr);
     return ap_check_launch("ap_deemphasis_f32");
@@ -1273,23 +1224,16 @@ int ap_deemphasis_ws_f32(const float *y, int64_t B, int64_t L, float coef, const
 
 int ap_savgol_f32(const float *x, int64_t outer, int64_t n, int64_t inner, const float *taps, int width, int mode,
                   float cval, const float *edge, float *out, void *stream) {
-    if (!x || !taps || !out) AP_FAIL(AP_ERR_INVALID, "delta: NULL buffer");
-    if (width < 3) AP_FAIL(AP_ERR_INVALID, "width must be >= 3, got %d", width);
-    if (width % 2 == 0) AP_FAIL(AP_ERR_INVALID, "width must be odd, got %d", width);
-    if (mode < AP_SG_INTERP || mode > AP_SG_WRAP) AP_FAIL(AP_ERR_INVALID, "delta: unknown mode");
-    if (outer <= 0 || n <= 0 || inner <= 0) AP_FAIL(AP_ERR_INVALID, "delta: empty array");
-    if (mode == AP_SG_INTERP && (!edge || width > n))
-        AP_FAIL(AP_ERR_INVALID, "when mode='interp', width=%d cannot exceed data.shape[axis]=%lld", width, (long long)n);
-    if (inner == 1 && width <= 64 && n < (1 << 30)) {       // contiguous axis: one row chunk per workgroup
-        const int64_t chunks = (n + AP_BLOCK * APSG_PER - 1) / (AP_BLOCK * APSG_PER);
-        if (outer * chunks <= kApMaxGrid) {
-            hipLaunchKernelGGL(ap_savgol_rows_kernel, dim3((unsigned)(outer * chunks)), dim3(AP_BLOCK), 0, (hipStream_t)stream,
-                               x, outer, (int)n, (int)chunks, taps, width, mode, cval, edge, out);
-            return ap_check_launch("ap_savgol_f32(rows)");
-        }
+    int64_t chunks = 0, grid = 0;
+    int rc = ap_prepare_savgol(x, outer, n, inner, taps, width, mode, edge, out, AP_BLOCK * APSG_PER, &chunks, &grid);
+    if (rc != AP_OK) return rc;
+    if (chunks > 0) {
+        hipLaunchKernelGGL(ap_savgol_rows_kernel, dim3((unsigned)grid), dim3(AP_BLOCK), 0, (hipStream_t)stream,
+                           x, outer, (int)n, (int)chunks, taps, width, mode, cval, edge, out);
+        return ap_check_launch("ap_savgol_f32(rows)");
     }
-    hipLaunchKernelGGL(ap_savgol_kernel, dim3(ap_grid_1d(outer * n * inner, AP_BLOCK, kApStreamGrid)), dim3(AP_BLOCK), 0,
-                       (hipStream_t)stream, x, outer, n, inner, taps, width, mode, cval, edge, out);
+    hipLaunchKernelGGL(ap_savgol_kernel, dim3((unsigned)grid), dim3(AP_BLOCK), 0, (hipStream_t)stream, x, outer, n, inner,
+                       taps, width, mode, cval, edge, out);
     return ap_check_launch("ap_savgol_f32");
 }
 
@@ -1349,12 +1293,9 @@ int ap_autocorrelation_f32(const float *y, int64_t B, int64_t n, int64_t max_lag
 
 int ap_spectral_contrast_f32(const float *S, int64_t B, int64_t F, int64_t T, const int32_t *bands_dev, int n_bands,
                              int linear, float *out, void *stream) {
-    if (!S || !bands_dev || !out) AP_FAIL(AP_ERR_INVALID, "spectral_contrast: NULL buffer");
-    if (B <= 0 || F <= 0 || T <= 0)
-        AP_FAIL(AP_ERR_INVALID, "S must be 2D (freq_bins, n_frames) or 3D (batch, freq_bins, n_frames)");
-    if (n_bands <= 0 || n_bands > 65535) AP_FAIL(AP_ERR_INVALID, "n_bands must be positive");
-    const int64_t blocks = (B * T + AP_BLOCK - 1) / AP_BLOCK;
-    if (blocks > kApMaxGrid) AP_FAIL(AP_ERR_UNSUPPORTED, "spectral_contrast: grid too large");
+    int64_t blocks = 0;
+    int rc = ap_prepare_spectral_contrast(S, B, F, T, bands_dev, n_bands, out, &blocks);
+    if (rc != AP_OK) return rc;
     hipLaunchKernelGGL(ap_spectral_contrast_kernel, dim3((unsigned)blocks, (unsigned)n_bands), dim3(AP_BLOCK), 0,
                        (hipStream_t)stream, S, B, F, T, bands_dev, linear, out);
     return ap_check_launch("ap_spectral_contrast_f32");
@@ -1362,19 +1303,19 @@ int ap_spectral_contrast_f32(const float *S, int64_t B, int64_t F, int64_t T, co
 
 int ap_acf_peaks_f32(const float *r, int64_t rows, int n_lag, int min_lag, int max_lag, float threshold, float sr,
                      float *f0, unsigned char *voiced, float *periodicity, void *stream) {
-    if (!r) AP_FAIL(AP_ERR_INVALID, "pitch: NULL buffer");
-    if (rows <= 0 || n_lag <= 0) AP_FAIL(AP_ERR_INVALID, "pitch: empty autocorrelation");
-    if (min_lag < 0) AP_FAIL(AP_ERR_INVALID, "pitch: negative lag");
-    hipLaunchKernelGGL(ap_acf_peak_kernel, dim3((unsigned)((rows + AP_BLOCK - 1) / AP_BLOCK)), dim3(AP_BLOCK), 0,
-                       (hipStream_t)stream, r, rows, n_lag, min_lag, max_lag, threshold, sr, f0, voiced, periodicity);
+    int64_t grid = 0;
+    int rc = ap_prepare_acf_peaks(r, rows, n_lag, min_lag, &grid);
+    if (rc != AP_OK) return rc;
+    hipLaunchKernelGGL(ap_acf_peak_kernel, dim3((unsigned)grid), dim3(AP_BLOCK), 0, (hipStream_t)stream, r, rows, n_lag,
+                       min_lag, max_lag, threshold, sr, f0, voiced, periodicity);
     return ap_check_launch("ap_acf_peaks_f32");
 }
 
 int ap_pcm16_to_f32(const int16_t *x, int64_t n, float scale, float *out, void *stream) {
-    if (n < 0 || (n > 0 && (!x || !out))) AP_FAIL(AP_ERR_INVALID, "pcm16_to_f32: bad buffer");
-    if (n == 0) return AP_OK;
-    hipLaunchKernelGGL(ap_pcm16_to_f32_kernel, dim3(ap_grid_1d((n + 7) / 8, AP_BLOCK, kApStreamGrid)), dim3(AP_BLOCK), 0,
-                       (hipStream_t)stream, x, n, scale, out);
+    int grid = 0;
+    int rc = ap_prepare_pcm16(x, n, out, &grid);
+    if (rc != AP_OK || grid == 0) return rc;
+    hipLaunchKernelGGL(ap_pcm16_to_f32_kernel, dim3(grid), dim3(AP_BLOCK), 0, (hipStream_t)stream, x, n, scale, out);
     return ap_check_launch("ap_pcm16_to_f32");
 }
 

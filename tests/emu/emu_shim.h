@@ -4,6 +4,19 @@
 // workgroups run one after another.  Used by tests/test_emu_kernels.py (and for
 // ASan/UBSan runs, which the GPU pool does not allow).  Never loaded by the
 // product package.
+//
+// LDS.  Dynamic LDS (`extern __shared__ char ap_smem[]`) is the 160 KB array below, guarded by
+// emu_lds_limit().  `__shared__` itself is defined away, so a STATIC `__shared__ float a[N]` inside a
+// kernel would become a private array of every emulated thread.  A translation unit that emulates such
+// kernels (kernels_features.h is the one header that has them; tests/emu/emu_features.cpp) includes the
+// headers that only use dynamic LDS first, then switches
+//     #undef __shared__
+//     #define __shared__ static
+// around the header with the static arrays: one instance per kernel, shared by all threads, which models
+// a workgroup's LDS because emu_launch runs the workgroups of a launch one after another.  The headers
+// included before the switch are `#pragma once` and are not read again, so their extern declaration of
+// ap_smem keeps its meaning.  Static arrays have no guard band: a twin that can size a tile checks it
+// against the array bound before it launches.
 #pragma once
 #include <barrier>
 #include <cmath>

@@ -391,6 +391,98 @@ def test_rms_zcr_block_kernel_vs_span_kernel_and_oracle(frame_length, hop, L, B,
     np.testing.assert_array_equal(z, ao.zero_crossing_rate(y, **kw))
 
 
+@pytest.mark.parametrize("frame_length,hop,L", [(64, 4, 1200), (1024, 64, 20000)])
+def test_rms_zcr_full_tile_large_batch(frame_length, hop, L):
+    """A batch large enough that the block kernel keeps its full tile: G = 256 - m + 1 = 241 frames per workgroup
+    (all 256 block slots) already gives >= 1024 workgroups, so the chip-filling loop never halves G.  The oracle on
+    a subsample of clips that holds the first and the last one; counts exact."""
+    B, m = 1100, frame_length // hop
+    G = 256 - m + 1
+    T = 1 + L // hop
+    assert m == 16 and G == 241 and T > G and ((T + G - 1) // G) * B >= 1024
+    rng = np.random.default_rng(L)
+    y = rng.standard_normal((B, L)).astype(np.float32)
+    y[0, 100:400] = 0.0
+    y[0, 250] = -0.0
+    pick = [0, 1, 255, 256, 777, B - 2, B - 1]
+    for pad_mode in ("constant", "edge"):
+        kw = dict(frame_length=frame_length, hop_length=hop, pad_mode=pad_mode)
+        r, z = ap.rms(dev(y), **kw), ap.zero_crossing_rate(dev(y), **kw)
+        assert r.shape == (B, 1, T) and z.shape == (B, 1, T)
+        np.testing.assert_allclose(host(r[pick]), ao.rms(y[pick], **kw), rtol=1e-5, atol=1e-7)
+        np.testing.assert_array_equal(host(z[pick]), ao.zero_crossing_rate(y[pick], **kw))
+
+
+def _offset_view(a, off=1):
+    """The contiguous array `a` on the device, starting `off` elements past a 16-byte boundary."""
+    flat = torch.zeros(a.size + 8, dtype=torch.float32, device="cuda")
+    v = flat[off:off + a.size].view(a.shape)
+    v.copy_(torch.from_numpy(np.ascontiguousarray(a)))
+    assert flat.data_ptr() % 16 == 0 and v.data_ptr() % 16 == off * a.itemsize and v.is_contiguous()
+    return v
+
+
+@pytest.mark.parametrize("L", [16384, 16385, 32768])
+def test_emphasis_from_pointers_off_the_16_byte_grid(L):
+    """Views that start 4 bytes past a 16-byte boundary reach the kernels as they are (contiguous: no copy), so the
+    one-sample pre-emphasis kernel and the 4-byte tile moves of de-emphasis run at lengths that otherwise take the
+    16-byte forms; L on a chunk border of de-emphasis, one past it, two chunks."""
+    rng = np.random.default_rng(L)
+    for shape in ((L,), (3, L)):
+        y = (rng.standard_normal(shape) * 0.1).astype(np.float32)
+        yd = _offset_view(y)
+        for zi in (None, 0.3):
+            p, zf = ap.preemphasis(yd, zi=zi, return_zf=True)
+            pw, zfw = ao.preemphasis(y, zi=zi, return_zf=True)
+            np.testing.assert_allclose(host(p), pw, rtol=1e-6, atol=1e-6)
+            np.testing.assert_array_equal(host(zf), zfw)
+            d, dzf = ap.deemphasis(yd, zi=zi, return_zf=True)
+            dw, dzfw = ao.deemphasis(y, zi=zi, return_zf=True)
+            scale = float(np.abs(dw).max())
+            np.testing.assert_allclose(host(d), dw, rtol=1e-4, atol=2e-5 * max(1.0, scale))
+            np.testing.assert_allclose(host(dzf), dzfw, rtol=1e-4, atol=2e-5 * max(1.0, scale))
+            np.testing.assert_array_equal(host(d), host(ap.deemphasis(dev(y), zi=zi)))     # 16-byte moves: same arithmetic
+
+
+@pytest.mark.parametrize("L", [16384, 16385, 32768])
+@pytest.mark.parametrize("coef", [0.97, 1.0])
+def test_deemphasis_on_chunk_borders(L, coef):
+    y = (np.random.default_rng(L + 1).standard_normal((2, L)) * 0.1).astype(np.float32)
+    for zi in (None, 0.3):
+        d, zf = ap.deemphasis(dev(y), coef=coef, zi=zi, return_zf=True)
+        dw, zfw = ao.deemphasis(y, coef=coef, zi=zi, return_zf=True)
+        scale = float(np.abs(dw).max())
+        np.testing.assert_allclose(host(d), dw, rtol=1e-4, atol=2e-5 * max(1.0, scale))
+        np.testing.assert_allclose(host(zf), zfw, rtol=1e-4, atol=2e-5 * max(1.0, scale))
+
+
+@pytest.mark.parametrize("shape", [(3, 2500), (2, 4097)])
+@pytest.mark.parametrize("width,order", [(9, 1), (63, 2)])
+def test_delta_rows_longer_than_one_chunk(shape, width, order):
+    """The contiguous-axis kernel gives a workgroup 1024 positions of a row: rows of several chunks, the last ragged."""
+    x = np.random.default_rng(shape[1]).standard_normal(shape).astype(np.float32)
+    for mode in ("interp", "nearest", "mirror", "constant", "wrap"):
+        np.testing.assert_allclose(host(ap.delta(dev(x), width=width, order=order, mode=mode, cval=0.75)),
+                                   ao.delta(x, width=width, order=order, mode=mode, cval=0.75), rtol=1e-4, atol=1e-4,
+                                   err_msg=mode)
+
+
+def test_delta_rows_shorter_than_the_filter_and_wide_filters():
+    rng = np.random.default_rng(3)
+    x = rng.standard_normal((13, 5)).astype(np.float32)                  # width 9 > 5 samples: SciPy allows all but 'interp'
+    for mode in ("nearest", "mirror", "constant", "wrap"):
+        np.testing.assert_allclose(host(ap.delta(dev(x), width=9, mode=mode, cval=-0.5)),
+                                   ao.delta(x, width=9, mode=mode, cval=-0.5), rtol=1e-4, atol=1e-4, err_msg=mode)
+    # width 65: more taps than the contiguous-axis kernel keeps in LDS, the generic kernel on the last axis
+    for shape in ((3, 200), (2, 40)):
+        x = rng.standard_normal(shape).astype(np.float32)
+        for mode in ("interp", "nearest", "mirror", "constant", "wrap"):
+            if mode == "interp" and shape[1] < 65:
+                continue
+            np.testing.assert_allclose(host(ap.delta(dev(x), width=65, mode=mode)), ao.delta(x, width=65, mode=mode),
+                                       rtol=1e-4, atol=1e-4, err_msg=mode)
+
+
 # ------------------------------------------------------------------ pitch_detect_acf / periodicity
 def _tones(B, L, sr, freqs, noise=0.02, seed=0):
     rng = np.random.default_rng(seed)

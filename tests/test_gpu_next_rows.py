@@ -63,6 +63,21 @@ def test_pcm16_edges_and_mfcc():
     np.testing.assert_allclose(host(got), want, rtol=1e-4, atol=2e-3)
 
 
+@pytest.mark.parametrize("n", [7, 8, 1000, 4099])
+def test_pcm16_from_a_view_on_an_odd_sample(n):
+    """A view that starts 2 bytes past a 16-byte boundary: the eight-samples-per-thread loads do not apply, every
+    sample takes the scalar form.  Exact, like the aligned route."""
+    x = _pcm((n + 1,), n)
+    x[1], x[-1] = -32768, 32767
+    x[n // 2] = -1
+    xd = dev(x)
+    v = xd[1:]
+    assert xd.data_ptr() % 16 == 0 and v.data_ptr() % 16 == 2 and v.is_contiguous()
+    got = ap.pcm16_to_float(v)
+    np.testing.assert_array_equal(host(got), x[1:].astype(np.float32) / 32768.0)
+    np.testing.assert_array_equal(host(got), host(ap.pcm16_to_float(dev(x[1:]))))
+
+
 def test_pcm16_headline_shape_full_scale_property():
     """Headline-shaped batch: scaling the PCM by 2 (exact in int16 here) scales the power mel by 4."""
     g = torch.Generator(device="cuda").manual_seed(9)
