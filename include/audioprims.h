@@ -548,6 +548,27 @@ int ap_yin_f32(const float *y /*dev (B,L)*/, int64_t B, int64_t L, int frame_len
 int ap_yin_cmnd_f32(const float *y /*dev (B,L)*/, int64_t B, int64_t L, int frame_length, int hop, int center,
                     int lo, int hi, const float *tw /*dev or NULL*/, float *out /*dev (B,hi-lo+1,T)*/, void *stream);
 
+/* hpss / hpss_medians (decompose.py; Fitzgerald 2010, librosa.decompose.hpss).  S: (B, F, T) float32, or complex
+ * pairs when is_complex, rows row_stride_in elements apart (>= T; the padding is never read).  With M = |S| (S itself
+ * when real):
+ *   harm[b,f,t] = element of rank k_harm / 2 (0-based, ascending) of M[b, f, r(t - k_harm/2 + j, T)], j < k_harm
+ *   perc[b,f,t] = the same along f with k_perc and r(., F)
+ *   r(i, n) = i mod 2n, mirrored as 2n - 1 - i when that is >= n  (scipy.ndimage mode="reflect")
+ *   softmask(X, R) = 0.5 (both margins 1) or 0 where max(X, R) < FLT_MIN, else with Z = max(X, R):
+ *                    (X/Z)^power / ((X/Z)^power + (R/Z)^power);  power = INFINITY: X > R as 0 / 1
+ *   mask_h = softmask(harm, perc * margin_harm),  mask_p = softmask(perc, harm * margin_perc)
+ * mode 0 stores the components S * mask_h, S * mask_p (of S's kind: complex pairs for a complex S), mode 1 the two
+ * masks, mode 2 the two medians (real); rows of the outputs are row_stride_out elements apart (>= T; the padding is
+ * never written).  Either output may be NULL (then it is not computed), not both.  k_harm, k_perc in 1 .. 255;
+ * ap_hpss_fused(k_harm, k_perc) != 0 (for (31, 31)) says the comparator-network kernel serves the sizes; general != 0
+ * forces the rank-counting kernel, which serves every size and returns the same bits.  Results are defined for finite,
+ * non-negative M.  AP_ERR_INVALID: sizes, strides, margins < 1, power <= 0, an output overlapping S or the other
+ * output; AP_ERR_UNSUPPORTED: F or T beyond 2^28, more than 2^31 - 1 tiles. */
+int ap_hpss_fused(int k_harm, int k_perc);
+int ap_hpss_f32(const float *S /*dev*/, int is_complex, int64_t B, int64_t F, int64_t T, int64_t row_stride_in,
+                int k_harm, int k_perc, float margin_harm, float margin_perc, float power, int mode, int general,
+                float *out_h /*dev or NULL*/, float *out_p /*dev or NULL*/, int64_t row_stride_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -58,6 +58,7 @@ ABI_SYMBOLS = [
     "ap_spectral_stats_f32", "ap_spectral_audio_fused", "ap_spectral_audio_f32", "ap_spectral_contrast_f32", "ap_frame_stats_f32", "ap_preemphasis_f32", "ap_deemphasis_f32", "ap_deemphasis_workspace_floats", "ap_deemphasis_ws_f32", "ap_savgol_f32",
     "ap_autocorrelation_nfft", "ap_autocorrelation_f32", "ap_acf_peaks_f32",
     "ap_yin_fused", "ap_yin_f32", "ap_yin_cmnd_f32",
+    "ap_hpss_fused", "ap_hpss_f32",
     "ap_pcm16_to_f32", "ap_melspec_pcm16_fused", "ap_melspec_pcm16_f32",
 ]
 
@@ -130,6 +131,8 @@ def _declare(lib) -> None:
         "ap_yin_fused": [I, I, L],
         "ap_yin_f32": [P, L, L, I, I, I, I, I, F, F, P, P, P, P],
         "ap_yin_cmnd_f32": [P, L, L, I, I, I, I, I, P, P, P],
+        "ap_hpss_fused": [I, I],
+        "ap_hpss_f32": [P, I, L, L, L, L, I, I, F, F, F, I, I, P, P, L, P],
         "ap_pcm16_to_f32": [P, L, F, P, P],
         "ap_melspec_pcm16_fused": [L, I, I, I, I, I, F, P],
         "ap_melspec_pcm16_f32": [P, L, L, I, I, P, P, I, I, L, P, P, P, I, F, P, P, P, P],

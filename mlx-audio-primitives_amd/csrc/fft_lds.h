@@ -131,6 +131,10 @@ AP_DEV ap_float2 ap_mul_fw_c(ap_float2 a, float c, float s) { return ap_mul_fw(a
 AP_DEV ap_float2 ap_mul_bw_c(ap_float2 a, float c, float s) { return ap_mul_bw(a, ap_mk(c, s)); }
 #endif
 
+// |v| as `magnitude` rounds it: one definition for ap_complex_unary_kernel / ap_complex_unary_rows_kernel and for the
+// kernels that take |S| on load (kernels_hpss.h), so that op(S) and op(magnitude(S)) see the same bits
+AP_DEV float ap_complex_abs(ap_float2 v) { return sqrtf(v.x * v.x + v.y * v.y); }
+
 // ---- forward butterflies, natural-order outputs ---------------------------------
 AP_DEV void ap_fft2(ap_float2 &a, ap_float2 &b) {
     ap_float2 t = ap_sub(a, b);

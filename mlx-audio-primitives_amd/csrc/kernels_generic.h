@@ -235,7 +235,7 @@ ap_complex_unary_kernel(const ap_float2 *S, int64_t n, int mode, float *out) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += stride) {
         const ap_float2 v = S[e];
-        out[e] = mode == 0 ? sqrtf(v.x * v.x + v.y * v.y) : atan2f(v.y, v.x);
+        out[e] = mode == 0 ? ap_complex_abs(v) : atan2f(v.y, v.x);
     }
 }
 
@@ -247,7 +247,7 @@ ap_complex_unary_rows_kernel(const ap_float2 *S, int64_t rows, int T, int Ts, in
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += stride) {
         const int64_t row = e / T;
         const ap_float2 v = S[row * Ts + (e - row * T)];
-        out[e] = mode == 0 ? sqrtf(v.x * v.x + v.y * v.y) : atan2f(v.y, v.x);
+        out[e] = mode == 0 ? ap_complex_abs(v) : atan2f(v.y, v.x);
     }
 }
 
