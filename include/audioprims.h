@@ -569,6 +569,41 @@ int ap_hpss_f32(const float *S /*dev*/, int is_complex, int64_t B, int64_t F, in
                 int k_harm, int k_perc, float margin_harm, float margin_perc, float power, int mode, int general,
                 float *out_h /*dev or NULL*/, float *out_p /*dev or NULL*/, int64_t row_stride_out, void *stream);
 
+/* onset_strength (onset.py; librosa.onset.onset_strength).  S: (B, M, T) float32, rows row_stride elements apart
+ * (>= T; the padding is never read); ref: NULL or an array of the same shape, rows ref_row_stride apart.
+ *   R[b,m,t] = ref[b,m,t], or without ref the maximum of S[b, r(j, M), t] over j in [m - max_size/2, m + (max_size-1)/2]
+ *              (r: SciPy's mode="reflect"; scipy.ndimage.maximum_filter1d along m; max_size in 1 .. 255, 1: S itself)
+ *   flux[b,u] = (1 / M) sum_m max(0, S[b, m, u + lag] - R[b, m, u]),   0 <= u < T - lag
+ *   out[b,t]  = flux[b, t - shift] for shift <= t < T, 0 for t < shift   (shift >= lag >= 1; out rows out_row_stride apart)
+ * db_mode != 0: S holds power and every value of S is replaced on load by
+ *   max(db_coef log10(max(s, db_amin) / max(db_ref, db_amin)), floor),  floor = that of max(S) - db_top_db
+ * with max(S) read from *smax_key (the order-preserving key ap_melspec_max_f32 / ap_reduce_max_f32 leave; db_top_db < 0:
+ * no floor): the values ap_to_db_f32 would store, bit for bit.  ref is never converted.  Results are defined for finite S.
+ * AP_ERR_INVALID: sizes, lag, max_size, shift < lag, strides, an output overlapping an input; AP_ERR_UNSUPPORTED: M or T
+ * beyond 2^28, more than 2^31 - 1 tiles of 64 frames. */
+int ap_onset_strength_f32(const float *S /*dev*/, int64_t B, int64_t M, int64_t T, int64_t row_stride,
+                          const float *ref /*dev or NULL*/, int64_t ref_row_stride, int lag, int max_size, int shift,
+                          int db_mode, float db_coef, float db_amin, float db_ref, float db_top_db,
+                          const uint32_t *smax_key /*dev or NULL*/, float *out /*dev (B,T)*/, int64_t out_row_stride,
+                          void *stream);
+
+/* peak_pick / onset_detect (onset.py; librosa.util.peak_pick, librosa.onset.onset_detect).  x: (B, T) float32, rows
+ * row_stride apart, T <= ap_peak_pick_max_frames() (AP_ERR_UNSUPPORTED beyond).  Per row, in one launch:
+ *   normalize != 0: x = (x - min x) / (max x - min x + FLT_MIN)
+ *   candidates: x[n] == max x[max(0, n - pre_max) : min(n + post_max, T)] and
+ *               x[n] >= mean x[max(0, n - pre_avg) : min(n + post_avg, T)] + delta   (float32 sum in index order)
+ *   kept, from the left: a candidate more than `wait` frames after the last kept one
+ *   backtrack != 0: a kept frame n moves to the largest k <= n with k = 0, or 1 <= k <= T - 2 and e[k] <= e[k-1] and
+ *               e[k] < e[k+1]; e = energy (rows energy_row_stride apart), or the values the candidates saw when NULL
+ *   guard != 0: a row that is all zero or holds a non-finite value keeps nothing (onset_detect)
+ * out_mask (B, T): 1 at the kept (moved) frames, 0 elsewhere; out_count (B) or NULL: the ones per row.
+ * pre_max, pre_avg, wait >= 0; post_max, post_avg >= 1. */
+int ap_peak_pick_max_frames(void);
+int ap_peak_pick_f32(const float *x /*dev*/, int64_t B, int64_t T, int64_t row_stride, int pre_max, int post_max,
+                     int pre_avg, int post_avg, float delta, int wait, int normalize, int guard, int backtrack,
+                     const float *energy /*dev or NULL*/, int64_t energy_row_stride, unsigned char *out_mask /*dev*/,
+                     int32_t *out_count /*dev or NULL*/, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -59,6 +59,7 @@ ABI_SYMBOLS = [
     "ap_autocorrelation_nfft", "ap_autocorrelation_f32", "ap_acf_peaks_f32",
     "ap_yin_fused", "ap_yin_f32", "ap_yin_cmnd_f32",
     "ap_hpss_fused", "ap_hpss_f32",
+    "ap_onset_strength_f32", "ap_peak_pick_max_frames", "ap_peak_pick_f32",
     "ap_pcm16_to_f32", "ap_melspec_pcm16_fused", "ap_melspec_pcm16_f32",
 ]
 
@@ -133,6 +134,9 @@ def _declare(lib) -> None:
         "ap_yin_cmnd_f32": [P, L, L, I, I, I, I, I, P, P, P],
         "ap_hpss_fused": [I, I],
         "ap_hpss_f32": [P, I, L, L, L, L, I, I, F, F, F, I, I, P, P, L, P],
+        "ap_onset_strength_f32": [P, L, L, L, L, P, L, I, I, I, I, F, F, F, F, P, P, L, P],
+        "ap_peak_pick_max_frames": [],
+        "ap_peak_pick_f32": [P, L, L, L, I, I, I, I, F, I, I, I, I, P, L, P, P, P],
         "ap_pcm16_to_f32": [P, L, F, P, P],
         "ap_melspec_pcm16_fused": [L, I, I, I, I, I, F, P],
         "ap_melspec_pcm16_f32": [P, L, L, I, I, P, P, I, I, L, P, P, P, I, F, P, P, P, P],

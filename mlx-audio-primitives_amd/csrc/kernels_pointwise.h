@@ -195,19 +195,7 @@ AP_KERNEL void __launch_bounds__(AP_BLOCK) ap_reduce_max_kernel(const float *x, 
 // top_db clip (convert.py:56-58: out = max(out, GLOBAL max(out) - top_db)): the conversion is
 // monotone, so max(out) = dB(max(S)) and the floor is known from a read-only max reduction of S
 // (*smax_key) before this single read+write pass.
-struct ApDbParams {
-    float coef, amin, ref_value, top_db;     // top_db < 0: no clip
-    const unsigned *ref_key, *smax_key;
-};
-AP_DEV float ap_db_ref(const ApDbParams &D) {
-    return fmaxf(D.ref_key ? ap_fkey_inv(*D.ref_key) : D.ref_value, D.amin);
-}
-AP_DEV float ap_db_value(const ApDbParams &D, float ref, float s) {
-    return D.coef * log10f(fmaxf(s, D.amin) / ref);
-}
-AP_DEV float ap_db_floor(const ApDbParams &D, float ref) {
-    return D.top_db >= 0.0f ? ap_db_value(D, ref, ap_fkey_inv(*D.smax_key)) - D.top_db : -INFINITY;
-}
+#include "ap_db.h"
 
 AP_KERNEL void __launch_bounds__(AP_BLOCK)
 ap_to_db_kernel(const float *S, int64_t n, ApDbParams D, float *out) {
