@@ -604,6 +604,57 @@ int ap_peak_pick_f32(const float *x /*dev*/, int64_t B, int64_t T, int64_t row_s
                      const float *energy /*dev or NULL*/, int64_t energy_row_stride, unsigned char *out_mask /*dev*/,
                      int32_t *out_count /*dev or NULL*/, void *stream);
 
+/* tempogram (rhythm.py; librosa.feature.tempogram): the windowed autocorrelation of an onset envelope per frame.
+ * env: (B, n) float32, rows row_stride apart; window: (W) on the device, W = win_length <= ap_tempogram_max_win()
+ * (AP_ERR_UNSUPPORTED beyond); h = W / 2.
+ *   center != 0: p = env between two linear ramps of h values, e[0] i / h and e[n-1] (h - 1 - j) / h (computed on load,
+ *                no padded copy), T = n;  center == 0: p = env, T = n - W + 1 (AP_ERR_INVALID when n < W)
+ *   x_t[i] = w[i] p[t + i];  ac[k, t] = sum_{i < W - k} x_t[i] x_t[i + k], 0 <= k < W, i ascending
+ *   norm != 0: tg = ac / max_k |ac[k, t]| per frame (left alone where that maximum is below FLT_MIN);  norm == 0: tg = ac
+ * out (B, W, T) or NULL: tg.  agg or NULL: ap_tempogram_agg_floats(B, n, W, center) floats, (B, ceil(T / 64), W):
+ * sum_t tg[k, t] over the 64 frames of every tile, added in frame order - what ap_tempo_pick_f32 joins into the mean
+ * without the tempogram ever being stored.  At least one of the two.
+ * tw selects the kernel: the twiddle table of ap_twiddle_table_host(1024) asks for the wave-per-frame kernel (W windowed
+ * values zero-padded to a 1024-point real transform, |A|^2, inverse: two on-chip transforms per frame; AP_ERR_UNSUPPORTED
+ * when ap_tempogram_fused(W) == 0, i.e. W > 512); NULL runs the general kernel (direct sums in float64, any W). */
+int ap_tempogram_max_win(void);
+int ap_tempogram_fused(int win_length);
+int64_t ap_tempogram_agg_floats(int64_t B, int64_t n, int win_length, int center);
+int ap_tempogram_f32(const float *env /*dev*/, int64_t B, int64_t n, int64_t row_stride, const float *window /*dev (W)*/,
+                     int win_length, int center, int norm, const float *tw /*dev or NULL*/, float *out /*dev or NULL*/,
+                     float *agg /*dev or NULL*/, void *stream);
+
+/* tempo (rhythm.py; librosa.feature.tempo): per column c of clip b, with
+ *   g[k] = (sum_{r < n_red} G[b clip_stride + k lag_stride + c col_stride + r red_stride]) / div      (r ascending)
+ * out_idx[b n_col + c] = the first k in 0 .. n_lags - 1 maximising log1p(1e6 g[k]) + logprior[k].  The strides serve
+ * the tile sums of ap_tempogram_f32 (n_red tiles, div = T), a stored tempogram's mean over frames (n_red = T,
+ * red_stride = 1, div = T) and its single frames (n_col = T, n_red = 1, div = 1). */
+int ap_tempo_pick_f32(const float *g /*dev*/, int64_t B, int64_t n_col, int n_lags, int64_t clip_stride, int64_t lag_stride,
+                      int64_t col_stride, int64_t n_red, int64_t red_stride, float div, const float *logprior /*dev (n_lags)*/,
+                      int32_t *out_idx /*dev (B, n_col)*/, void *stream);
+
+/* beat_track (rhythm.py; librosa.beat.beat_track, Ellis 2007).  env: (B, T) float32, rows row_stride apart,
+ * T <= ap_beat_track_max_frames() (AP_ERR_UNSUPPORTED beyond); period (B) on the device: the beat period P of every row
+ * in frames.  Per row, one workgroup, with h = rint(P / 2) (halves to even):
+ *   o'[i]   = o[i] / std(o, ddof = 1)
+ *   L[i]    = sum_{k = -P .. P} exp(-0.5 (32 k / P)^2) o'[i - k]                    (o' = 0 outside the row)
+ *   C[i]    = L[i] + max_{d = 2P, 2P - 1, .., h} (-tightness ln(d / P)^2 + C[i - d]),  C[j] = 0 for j < 0
+ *   link[i] = i - d of the first maximum in that order; -1 while no frame j <= i has had L[j] >= 0.01 max(L)
+ *   M[i]    = C[i] > C[i-1] and C[i] >= C[i+1] (M[0] = 0, M[T-1] = C[T-1] > C[T-2])
+ *   tail    = the largest i with M[i] and 2 C[i] > median{C[j] : M[j]};  beats = tail, link[tail], .. while >= 0, reversed
+ *   s[j]    = 0.5 L[b[j-1]] + L[b[j]] + 0.5 L[b[j+1]];  kept: b[lo .. hi], lo / hi the first / last j with
+ *             s[j] > (trim ? 0.5 sqrt(mean s^2) : 0), both inclusive
+ * A row that is all zero, holds a non-finite value, has zero deviation or T < 2, has no M[i] or no s[j] above the
+ * threshold keeps nothing.  out_mask (B, T): 1 at the kept beats; out_count (B): their number, or -1 (and no beats) for
+ * a row whose period lies outside 2 .. ap_beat_track_max_period().  out_L, out_C, out_link (B, T) or NULL: the
+ * intermediates (0, 0, -1 for a row that keeps nothing before the dynamic programme). */
+int ap_beat_track_max_frames(void);
+int ap_beat_track_max_period(void);
+int ap_beat_track_f32(const float *env /*dev*/, int64_t B, int64_t T, int64_t row_stride, const int32_t *period /*dev (B)*/,
+                      float tightness, int trim, unsigned char *out_mask /*dev*/, int32_t *out_count /*dev*/,
+                      float *out_L /*dev or NULL*/, float *out_C /*dev or NULL*/, int32_t *out_link /*dev or NULL*/,
+                      void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -60,6 +60,8 @@ ABI_SYMBOLS = [
     "ap_yin_fused", "ap_yin_f32", "ap_yin_cmnd_f32",
     "ap_hpss_fused", "ap_hpss_f32",
     "ap_onset_strength_f32", "ap_peak_pick_max_frames", "ap_peak_pick_f32",
+    "ap_tempogram_max_win", "ap_tempogram_fused", "ap_tempogram_agg_floats", "ap_tempogram_f32", "ap_tempo_pick_f32",
+    "ap_beat_track_max_frames", "ap_beat_track_max_period", "ap_beat_track_f32",
     "ap_pcm16_to_f32", "ap_melspec_pcm16_fused", "ap_melspec_pcm16_f32",
 ]
 
@@ -137,6 +139,13 @@ def _declare(lib) -> None:
         "ap_onset_strength_f32": [P, L, L, L, L, P, L, I, I, I, I, F, F, F, F, P, P, L, P],
         "ap_peak_pick_max_frames": [],
         "ap_peak_pick_f32": [P, L, L, L, I, I, I, I, F, I, I, I, I, P, L, P, P, P],
+        "ap_tempogram_max_win": [],
+        "ap_tempogram_fused": [I],
+        "ap_tempogram_f32": [P, L, L, L, P, I, I, I, P, P, P, P],
+        "ap_tempo_pick_f32": [P, L, L, I, L, L, L, L, L, F, P, P, P],
+        "ap_beat_track_max_frames": [],
+        "ap_beat_track_max_period": [],
+        "ap_beat_track_f32": [P, L, L, L, P, F, I, P, P, P, P, P, P],
         "ap_pcm16_to_f32": [P, L, F, P, P],
         "ap_melspec_pcm16_fused": [L, I, I, I, I, I, F, P],
         "ap_melspec_pcm16_f32": [P, L, L, I, I, P, P, I, I, L, P, P, P, I, F, P, P, P, P],
@@ -156,6 +165,8 @@ def _declare(lib) -> None:
     lib.ap_resample_poly_pad_samples.restype = L
     lib.ap_deemphasis_workspace_floats.argtypes = [L, L]
     lib.ap_deemphasis_workspace_floats.restype = L
+    lib.ap_tempogram_agg_floats.argtypes = [L, L, I, I]
+    lib.ap_tempogram_agg_floats.restype = L
     lib.ap_mse_workspace_doubles.argtypes = []
     lib.ap_mse_workspace_doubles.restype = L
 
