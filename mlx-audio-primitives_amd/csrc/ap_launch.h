@@ -301,8 +301,9 @@ static inline int ap_prepare_mel_run(ApMelWaveParams &W, const ApStftParams &P, 
     if (pass < 1 || pass > 4 || W.n_quads < 256 * pass) return 1;   // a pass reads 4 weight quads per lane
     *n_pass = pass;
     int off = n_waves * x_complex * (int)sizeof(ap_float2);
-    W.off_tw2 = off; off += APW_TW2_COMPLEX * (int)sizeof(ap_float2);
-    W.off_tw1 = off; off += 16 * 64 * (int)sizeof(ap_float2);
+    // twiddle tables in rows of 18 complex (apm_fill_tables): 16-byte aligned rows for ds_read_b128
+    W.off_tw2 = off; off += APM_TW2_COMPLEX * (int)sizeof(ap_float2);
+    W.off_tw1 = off; off += APM_TW1_COMPLEX * (int)sizeof(ap_float2);
     W.off_win = off; off += APW_NC * (int)sizeof(ap_float2);
     W.off_wq = off; off += ap_align16(W.n_quads * 16);
     W.off_parts = off;
@@ -336,8 +337,8 @@ static inline int ap_prepare_spec_run(ApSpecWaveParams &W, const ApStftParams &P
     W.pad = P.pad;
     W.hopj = P.hop == 512 ? 4 : 0;
     int off = n_waves * x_complex * (int)sizeof(ap_float2);
-    W.off_tw2 = off; off += APW_TW2_COMPLEX * (int)sizeof(ap_float2);
-    W.off_tw1 = off; off += 16 * 64 * (int)sizeof(ap_float2);
+    W.off_tw2 = off; off += APM_TW2_COMPLEX * (int)sizeof(ap_float2);     // rows of 18 complex, as in ap_prepare_mel_run
+    W.off_tw1 = off; off += APM_TW1_COMPLEX * (int)sizeof(ap_float2);
     W.off_win = off; off += APW_NC * (int)sizeof(ap_float2);
     W.lds_bytes = off;
     if (off > AP_LDS_MAX) return 1;

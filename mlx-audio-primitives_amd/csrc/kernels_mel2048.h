@@ -22,6 +22,8 @@
 //     the paired real split take the lane's 16 bins without another LDS round trip - 32 packed adds
 //     and 8 selects instead of the 64 v_fmac_f32_dpp, 32 v_cndmask and the s_nop pads of the DPP
 //     quad stage (apm_quad8), and 8 ds_read_b128 instead of 17 ds_read_b64 for the split;
+//   * the two twiddle tables are rows of 18 complex per lane (apm_fill_tables): eight aligned
+//     ds_read_b128 per table and frame instead of 15 paired 8-byte reads at half the LDS rate;
 //   * the 8-frame output run of a lane's two mel rows lives in registers (32 contiguous bytes per
 //     row and lane, as in ap_mel1024_wave_kernel): no output tile in LDS; the partial sums
 //     alias the idle upper half of the wave's exchange buffer.
@@ -78,10 +80,36 @@ AP_DEV ApmPairLane apm_pair_lane_init(int lane) {
 }
 
 // forward transform of apw_forward up to the W_64 twiddles; the last radix-4 is left to apm_split,
-// the exchange hands it whole groups.  tw2row holds plain W_64^(a c) rows (apw_fill_tables<false>).
+// the exchange hands it whole groups.  tw1row / tw2row: the lane's rows of the two twiddle tables in the
+// 18-complex layout of apm_fill_tables (W_1024^(lane k) and plain W_64^(a c)), 16-byte aligned: eight
+// ds_read_b128 each (entry 0 = W^0 is read and not used).
+#ifdef AP_PACKED_COMPLEX
+// (as vector loads: read through the ap_float4 struct the four floats become a chain of scalar loads, and with
+// entry 0 dead the chain starts 8 bytes into the row and comes out as 8-byte pairs again)
+typedef float apm_float4v __attribute__((ext_vector_type(4)));
+AP_DEV void apm_load_row(const ap_float2 *row, ap_float2 (&t)[16]) {
+    const apm_float4v *src = reinterpret_cast<const apm_float4v *>(row);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const apm_float4v v = src[j];
+        t[2 * j] = __builtin_shufflevector(v, v, 0, 1);
+        t[2 * j + 1] = __builtin_shufflevector(v, v, 2, 3);
+    }
+}
+#else
+AP_DEV void apm_load_row(const ap_float2 *row, ap_float2 (&t)[16]) {
+    const ap_float4 *src = reinterpret_cast<const ap_float4 *>(row);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const ap_float4 v = src[j];
+        t[2 * j] = ap_mk(v.x, v.y);
+        t[2 * j + 1] = ap_mk(v.z, v.w);
+    }
+}
+#endif
 // (the samples x and the window pairs w go in separately: the window rides on the first butterfly level)
 template <int REGS>
-AP_DEV void apm_forward(const ap_float2 (&x)[16], const ap_float2 (&w)[16], ap_float2 *X, const ap_float2 *TW1,
+AP_DEV void apm_forward(const ap_float2 (&x)[16], const ap_float2 (&w)[16], ap_float2 *X, const ap_float2 *tw1row,
                         const ap_float2 *tw2row, const ap_float2 (&t1r)[16], const ap_float2 (&t2r)[16],
                         const ApwLane &c) {
     const int lane = c.lane;
@@ -92,8 +120,7 @@ AP_DEV void apm_forward(const ap_float2 (&x)[16], const ap_float2 (&w)[16], ap_f
         for (int k = 1; k < 16; ++k) v[k] = ap_mul_fw(v[k], t1r[k]);
     } else {
         ap_float2 t1[16];
-#pragma unroll
-        for (int k = 1; k < 16; ++k) t1[k] = TW1[k * 64 + lane];
+        apm_load_row(tw1row, t1);
         ApButterfly<16>::run_weighted(x, w, v);
 #pragma unroll
         for (int k = 1; k < 16; ++k) v[k] = ap_mul_fw(v[k], t1[k]);
@@ -107,10 +134,7 @@ AP_DEV void apm_forward(const ap_float2 (&x)[16], const ap_float2 (&w)[16], ap_f
     ap_float2 t2[16];
 #pragma unroll
     for (int i = 0; i < 16; ++i) v[i] = X[APW_T1(lane) + i];
-    if (!(REGS & APM_REG_TW2)) {
-#pragma unroll
-        for (int cc = 1; cc < 16; ++cc) t2[cc] = tw2row[cc];
-    }
+    if (!(REGS & APM_REG_TW2)) apm_load_row(tw2row, t2);
     AP_WAVE_SYNC();
     ApButterfly<16>::run(v);
 #pragma unroll
@@ -214,8 +238,8 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) ap_mel2048_run_kernel(ApMelWa
     const int lane = tid & 63;
     const int wave = AP_UNIFORM(tid >> 6);
     ap_float2 *X = reinterpret_cast<ap_float2 *>(ap_smem) + wave * APW_X_COMPLEX;
-    ap_float2 *TW2 = reinterpret_cast<ap_float2 *>(ap_smem + P.off_tw2);               // [4][17], signed
-    const ap_float2 *TW1 = reinterpret_cast<const ap_float2 *>(ap_smem + P.off_tw1);   // [16][64]
+    ap_float2 *TW2 = reinterpret_cast<ap_float2 *>(ap_smem + P.off_tw2);               // [4][18]
+    const ap_float2 *TW1 = reinterpret_cast<const ap_float2 *>(ap_smem + P.off_tw1);   // [64][18]
     const ap_float2 *WIN = reinterpret_cast<const ap_float2 *>(ap_smem + P.off_win);   // [1024] pairs
     const ap_float4 *WQ = reinterpret_cast<const ap_float4 *>(ap_smem + P.off_wq);     // [n_quads]
     float *pp = reinterpret_cast<float *>(X);                 // |X|^p plane of this wave (floats 0..1024)
@@ -227,11 +251,11 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) ap_mel2048_run_kernel(ApMelWa
         const int nt = 64 * NW;
         ap_float4 *wq = reinterpret_cast<ap_float4 *>(ap_smem + P.off_wq);
         for (int i = tid; i < P.n_quads; i += nt) wq[i] = reinterpret_cast<const ap_float4 *>(P.quads)[i];
-        apw_fill_tables<false>(TW2, reinterpret_cast<ap_float2 *>(ap_smem + P.off_tw1),
-                               reinterpret_cast<ap_float2 *>(ap_smem + P.off_win), P.tw, P.window, tid, nt);
+        apm_fill_tables(TW2, reinterpret_cast<ap_float2 *>(ap_smem + P.off_tw1),
+                        reinterpret_cast<ap_float2 *>(ap_smem + P.off_win), P.tw, P.window, tid, nt);
     }
     AP_LDS_BARRIER();
-    const ApwLane lc = apw_lane_init(lane, TW2, P.tw);
+    const ApwLane lc = apw_lane_init(lane, TW2, P.tw, APM_TW_ROW);
     const ApmPairLane pl = apm_pair_lane_init(lane);
     // per-lane tables kept in registers (REGS): straight from the global tables
     ap_float2 winr[16], t1r[16], t2r[16], wsp[8];
@@ -347,7 +371,7 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) ap_mel2048_run_kernel(ApMelWa
                     for (int j = 0; j < 16; ++j) ws[j] = WIN[lane + 64 * j];
                 }
                 AP_SCHED_FENCE();
-                apm_forward<REGS>(xs, ws, X, TW1, lc.tw2row, t1r, t2r, lc);
+                apm_forward<REGS>(xs, ws, X, TW1 + APM_TW_ROW * lane, lc.tw2row, t1r, t2r, lc);
             }
             // The next frame of this wave's stretch, in flight during split + contraction
             AP_SCHED_FENCE();
@@ -517,10 +541,10 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) ap_spec2048_run_kernel(ApSpec
     const ap_float2 *TW1 = reinterpret_cast<const ap_float2 *>(ap_smem + P.off_tw1);
     const ap_float2 *WIN = reinterpret_cast<const ap_float2 *>(ap_smem + P.off_win);
     float *pp = reinterpret_cast<float *>(X);                 // |X|^p plane of this wave (floats 0..1024)
-    apw_fill_tables<false>(TW2, reinterpret_cast<ap_float2 *>(ap_smem + P.off_tw1),
-                           reinterpret_cast<ap_float2 *>(ap_smem + P.off_win), P.tw, P.window, tid, 64 * NW);
+    apm_fill_tables(TW2, reinterpret_cast<ap_float2 *>(ap_smem + P.off_tw1),
+                    reinterpret_cast<ap_float2 *>(ap_smem + P.off_win), P.tw, P.window, tid, 64 * NW);
     AP_LDS_BARRIER();
-    const ApwLane lc = apw_lane_init(lane, TW2, P.tw);
+    const ApwLane lc = apw_lane_init(lane, TW2, P.tw, APM_TW_ROW);
     const ApmPairLane pl = apm_pair_lane_init(lane);
     ap_float2 winr[16], t1r[16], t2r[16], wsp[8];
 #pragma unroll
@@ -574,7 +598,7 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) ap_spec2048_run_kernel(ApSpec
                 for (int j = 0; j < 16; ++j) ws[j] = WIN[lane + 64 * j];
             }
             AP_SCHED_FENCE();
-            apm_forward<REGS>(xs, ws, X, TW1, lc.tw2row, t1r, t2r, lc);
+            apm_forward<REGS>(xs, ws, X, TW1 + APM_TW_ROW * lane, lc.tw2row, t1r, t2r, lc);
         }
         AP_SCHED_FENCE();
         if (more) {

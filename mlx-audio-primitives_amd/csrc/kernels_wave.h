@@ -171,7 +171,8 @@ struct ApwLane {
     ap_float2 half, halfc;         // (1/2, 1/2), (1/2, -1/2)
 };
 
-AP_DEV ApwLane apw_lane_init(int lane, const ap_float2 *TW2, const ap_float2 *tw) {
+// (tw2_stride: complex per row of TW2 - 17 for apw_fill_tables, APM_TW_ROW for apm_fill_tables)
+AP_DEV ApwLane apw_lane_init(int lane, const ap_float2 *TW2, const ap_float2 *tw, int tw2_stride = 17) {
     ApwLane c;
     c.lane = lane;
     c.qa = lane & 3;                              // position in the quad
@@ -180,7 +181,7 @@ AP_DEV ApwLane apw_lane_init(int lane, const ap_float2 *TW2, const ap_float2 *tw
     c.rotw = c.qa == 3 ? ap_mk(0.0f, 1.0f) : ap_mk(1.0f, 0.0f);   // lane 3 multiplies by -i between stages
     c.qd = ((c.qa & 1) << 1) | (c.qa >> 1);       // output digit held by this lane
     c.k1p = lane >> 2;
-    c.tw2row = TW2 + c.qa * 17;
+    c.tw2row = TW2 + c.qa * tw2_stride;
     c.tws0h = ap_scale(tw[lane], 0.5f);
     c.half = ap_mk(0.5f, 0.5f);
     c.halfc = ap_mk(0.5f, -0.5f);
@@ -198,6 +199,24 @@ AP_DEV void apw_fill_tables(ap_float2 *tw2, ap_float2 *tw1, ap_float2 *win, cons
         tw2[a * 17 + (tid & 15)] = ap_scale(tw[32 * a * (tid & 15)], (QUAD_SIGNS && (a == 1 || a == 2)) ? -1.0f : 1.0f);
     }
     for (int i = tid; i < 16 * 64; i += nt) tw1[i] = tw[2 * (i & 63) * (i >> 6)];
+    for (int i = tid; i < APW_NC; i += nt) win[i] = reinterpret_cast<const ap_float2 *>(window)[i];
+}
+
+// The same tables for the run kernels (kernels_mel2048.h), in rows of APM_TW_ROW = 18 complex (144 bytes):
+// W_64^(a c) [4][18] and W_1024^(lane k) [64][18], entry k of a row at k < 16, the last two zero.  A lane's
+// 15 twiddles are then eight aligned 16-byte reads (entry 0 = W^0 rides along unused) instead of 15 8-byte
+// reads at half the LDS rate, and the row stride of 36 dwords keeps the reads conflict-free (tools/lds_banks.py).
+// Same values as apw_fill_tables<false>.
+AP_DEV void apm_fill_tables(ap_float2 *tw2, ap_float2 *tw1, ap_float2 *win, const ap_float2 *tw,
+                            const float *window, int tid, int nt) {
+    if (tid < APM_TW2_COMPLEX) {
+        const int a = tid / APM_TW_ROW, c = tid % APM_TW_ROW;
+        tw2[tid] = c < 16 ? tw[32 * a * c] : ap_mk(0.0f, 0.0f);
+    }
+    for (int i = tid; i < APM_TW1_COMPLEX; i += nt) {
+        const int l = i / APM_TW_ROW, k = i % APM_TW_ROW;
+        tw1[i] = k < 16 ? tw[2 * l * k] : ap_mk(0.0f, 0.0f);
+    }
     for (int i = tid; i < APW_NC; i += nt) win[i] = reinterpret_cast<const ap_float2 *>(window)[i];
 }
 

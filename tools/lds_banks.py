@@ -51,3 +51,16 @@ if __name__ == "__main__":
         w = sum(cycles("w64", ((k1 * 4 + a) * S + b) * 8) for k1 in range(16))
         r = sum(cycles("r128", (lanes * S + 2 * i) * 8) for i in range(8)) if S % 2 == 0 else -1
         print(f"exch1 S={S}: write {w} (ideal 64)  read {r} (ideal 32)")
+    # twiddle rows of the n_fft = 2048 run kernels: one row of S complex per lane, eight ds_read_b128 per lane
+    for S in (16, 18, 20):
+        r = sum(cycles("r128", (lanes * S + 2 * i) * 8) for i in range(8))
+        print(f"tw1 rows S={S}: read {r} bank cycles (ideal 32) for 8 ds_read_b128 = 8 x 1024 bytes")
+    # The old [16][64] table: 15 ds_read_b64 of consecutive lanes.  cycles() counts BANK passes only (one per
+    # group of lanes without a conflict), not the issue rate of the instruction form: 30 conflict-free passes
+    # here move 15 x 512 bytes, 256 bytes per pass, the rows above 32 passes of 256 bytes.  The compiler pairs
+    # these reads into ds_read2st64_b64 / ds_read2_b64, which the guide's instruction table rates at 128
+    # bytes per clock against 256 for ds_read_b128: that rate, not conflicts, is what the row layout buys
+    # (measured: SQ_LDS_IDX_ACTIVE -54 per frame for the two tables, profiles/README.md "Round 5").
+    r = sum(cycles("r64", (k * 64 + lanes) * 8) for k in range(1, 16))
+    print(f"tw1 [16][64]: read {r} bank cycles (ideal 30) for 15 ds_read_b64 = 15 x 512 bytes; "
+          f"at the paired forms' 128 B/clk: {15 * 512 // 128} clocks against {8 * 1024 // 256} for the rows")
