@@ -655,6 +655,25 @@ int ap_beat_track_f32(const float *env /*dev*/, int64_t B, int64_t T, int64_t ro
                       float *out_L /*dev or NULL*/, float *out_C /*dev or NULL*/, int32_t *out_link /*dev or NULL*/,
                       void *stream);
 
+/* pcen (pcen.py, streaming.py: StreamingPCEN; librosa.pcen, Wang et al. 2017).  S: (B, M, T) float32 >= 0, rows
+ * row_stride elements apart (>= T; the padding is never read); ref: NULL or an array of the same shape, rows
+ * ref_row_stride apart; out: the same shape, rows out_row_stride apart (the padding is never written).  With a = 1 - b:
+ *   R[b,m,t] = ref[b,m,t], or without ref the maximum of S[b, r(j, M), t] over j in [m - max_size/2, m + (max_size-1)/2]
+ *              (r: SciPy's mode="reflect"; scipy.ndimage.maximum_filter1d along m; max_size in 1 .. 255, 1: S itself)
+ *   Msm[t]   = b R[t] + a Msm[t-1],  a Msm[-1] = zi[b M + m]  (NULL: 1 - b, the steady state of a unit input, for every row)
+ *   smooth   = (eps + Msm)^-gain
+ *   out      = (S smooth + bias)^power - bias^power, evaluated as bias^power expm1(power log1p(S smooth / bias));
+ *              log1p(S smooth) when power = 0; (S smooth)^power when bias = 0
+ *   zf[b M + m] = a Msm[T-1]  (NULL: not wanted): the zi of the call that continues the rows
+ * b crosses as a double: the float32 powers a^k, k <= 64, that the kernel's scan multiplies by are rounded from float64
+ * powers.  One launch, one read of S (and ref) and one write of out; results are defined for finite S >= 0.
+ * AP_ERR_INVALID: sizes, b outside [0, 1], b = 0 without zi, negative gain / bias / power, eps below FLT_MIN, max_size, strides,
+ * an output overlapping an input; AP_ERR_UNSUPPORTED: M or T beyond 2^28. */
+int ap_pcen_f32(const float *S /*dev*/, int64_t B, int64_t M, int64_t T, int64_t row_stride,
+                const float *ref /*dev or NULL*/, int64_t ref_row_stride, int max_size, double b, float gain, float bias,
+                float power, float eps, const float *zi /*dev (B*M) or NULL*/, float *out /*dev*/, int64_t out_row_stride,
+                float *zf /*dev (B*M) or NULL*/, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,6 +21,8 @@ import torch
 
 from . import _extension as _x
 from .mel import melspectrogram
+from .onset import _spectrum
+from .pcen import _axes as _pcen_axes, _parameters as _pcen_parameters, _run as _pcen_run
 from .stft import _get_padded_window, _get_twiddles, _padded_row_stride, _resolve_stft_args, stft
 
 
@@ -200,4 +202,44 @@ class StreamingISTFT:
             raise ValueError("flush() before any frame")
         out = self._run(None, 0, final=True)
         self._flushed = True
+        return out
+
+
+class StreamingPCEN:
+    """Incremental ``pcen``: feed (M, T) or (batch, M, T) spectrogram chunks (the mel frames of a ``StreamingSTFT``,
+    scaled as the model expects); every row's filter state (zf) stays on the device between calls, so the chunks
+    equal the offline call on all frames to rounding, whatever the chunking.  Takes the parameters of ``pcen``;
+    ``zi`` is the state the stream (and every ``reset()``) starts from.  max_size > 1 is allowed: the maximum runs
+    over bins, not time.  ref= is not taken: a reference array has no streaming counterpart."""
+
+    def __init__(self, *, sr: float = 22050, hop_length: int = 512, gain: float = 0.98, bias: float = 2,
+                 power: float = 0.5, time_constant: float = 0.400, eps: float = 1e-6, b=None, max_size: int = 1,
+                 axis: int = -1, max_axis=None, zi=None):
+        self.b, self.gain, self.bias, self.power, self.eps, self.max_size = _pcen_parameters(
+            sr, hop_length, gain, bias, power, time_constant, eps, b, max_size, axis, max_axis, zi is not None)
+        self._axis, self._max_axis = int(axis), None if max_axis is None else int(max_axis)
+        self._zi = zi
+        self.reset()
+
+    def reset(self) -> None:
+        """Forget the kept state: the next chunk starts a new stream."""
+        self._state = self._zi
+        self._shape = None
+        self.frames_consumed = 0
+
+    def process(self, S_chunk) -> torch.Tensor:
+        """Feed the next frames; returns their normalised values, of the chunk's shape."""
+        S, two_d = _spectrum(S_chunk, "S_chunk")
+        _pcen_axes(S.ndim, self._axis, self._max_axis, self.max_size)
+        lead = tuple(S.shape[:-1])
+        if self._shape is None:
+            self._shape = lead
+        elif lead != self._shape:
+            raise ValueError(f"every chunk must have the same leading shape: got {lead} after {self._shape}")
+        if S.shape[-1] == 0:                                      # nothing to do, the state stays
+            dev = S.device if S.is_cuda else _x.require_device()
+            return torch.empty(S.shape, dtype=torch.float32, device=dev)
+        out, self._state = _pcen_run(S, two_d, None, self._state, True, self.b, self.gain, self.bias, self.power,
+                                     self.eps, self.max_size)
+        self.frames_consumed += int(S.shape[-1])
         return out
