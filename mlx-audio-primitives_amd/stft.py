@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _extension as _x
-from .windows import get_window
+from .windows import _cached_window, get_window
 
 _WINDOW_SUM_EPSILON = 1e-8      # stft.py:21 (applied inside the overlap-add kernel)
 _WINDOW_CACHE_MAXSIZE = 32      # stft.py:24
@@ -63,12 +63,17 @@ def _get_padded_window(window, win_length: int, n_fft: int, device) -> torch.Ten
     hit = _padded_window_cache.get(key)
     if hit is not None:
         return hit
-    win = get_window(window, win_length, fftbins=True, device=device).to(device)
+    src = _cached_window(window, win_length, fftbins=True, device=device)
+    win = src.to(device)
     if win_length < n_fft:
         left = (n_fft - win_length) // 2
         right = n_fft - win_length - left
         win = torch.nn.functional.pad(win, (left, right))
     win = win.contiguous()
+    # the cache owns its tensors: a caller's array window that needed no conversion is cloned, or writing to it
+    # later would change what every equal-valued window hits (named windows are windows.py's own cached tensors)
+    if not isinstance(window, str) and win.untyped_storage().data_ptr() == src.untyped_storage().data_ptr():
+        win = win.clone()
     _padded_window_cache.put(key, win)
     return win
 

@@ -44,7 +44,15 @@ def get_window(window, n_fft: int, fftbins: bool = True, device=None) -> torch.T
     """Window of shape (n_fft,), float32 (reference windows.py:192-256).
 
     ``window`` is a name or a 1-D tensor/array of length n_fft (passed through as
-    float32).  Host-built; lands on the current HIP device when there is one."""
+    float32).  Host-built; lands on the current HIP device when there is one.
+    A named window is a copy of the cached tensor: the caller may write to it."""
+    t = _cached_window(window, n_fft, fftbins, device)
+    return t.clone() if isinstance(window, str) else t
+
+
+def _cached_window(window, n_fft: int, fftbins: bool = True, device=None) -> torch.Tensor:
+    """`get_window` for this package's own callers, which only read: a named window is the per-device cached
+    tensor itself, an array window the caller's tensor (converted if need be)."""
     if isinstance(window, (torch.Tensor, np.ndarray)):
         if window.shape[0] != n_fft:
             raise ValueError(

@@ -69,6 +69,31 @@ def test_host_windows_match_scipy_and_oracle():
                                   ext.generate_window_host("hann", 65, False)[:64])
 
 
+def test_named_windows_are_handed_out_as_copies():
+    """get_window(name, ...) returns a copy of the per-device cached tensor: writing to it must not change what
+    later callers (stft's padded-window cache among them) get.  Host tensors here; the cache is the same code."""
+    import importlib
+
+    stft_mod = importlib.import_module("mlx_audio_primitives_amd.stft")
+    want = ao.get_window("hamming", 333)
+    w = ap.get_window("hamming", 333, device="cpu")
+    np.testing.assert_array_equal(w.numpy(), want)
+    w.mul_(0)
+    np.testing.assert_array_equal(ap.get_window("hamming", 333, device="cpu").numpy(), want)
+    assert ap.get_window("hamming", 333, device="cpu").data_ptr() != ap.get_window("hamming", 333, device="cpu").data_ptr()
+    # the padded-window cache: a named window (padded and not), then the caller's own tensor
+    for n_fft in (333, 400):
+        p = stft_mod._get_padded_window("hamming", 333, n_fft, "cpu")
+        np.testing.assert_array_equal(p.numpy(), ao.padded_window("hamming", 333, n_fft))
+    mine = ap.get_window("hamming", 333, device="cpu")
+    first = stft_mod._get_padded_window(mine, 333, 333, "cpu")
+    assert first.data_ptr() != mine.data_ptr()
+    mine.mul_(2)
+    again = stft_mod._get_padded_window(ap.get_window("hamming", 333, device="cpu"), 333, 333, "cpu")     # same values: a hit
+    np.testing.assert_array_equal(again.numpy(), want)
+    np.testing.assert_array_equal(stft_mod._get_padded_window(mine, 333, 333, "cpu").numpy(), 2 * want)
+
+
 def test_host_mel_filterbank():
     z = load_golden("mel_filters.npz")
     for row in z["meta"]:
