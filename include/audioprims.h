@@ -674,6 +674,22 @@ int ap_pcen_f32(const float *S /*dev*/, int64_t B, int64_t M, int64_t T, int64_t
                 float power, float eps, const float *zi /*dev (B*M) or NULL*/, float *out /*dev*/, int64_t out_row_stride,
                 float *zf /*dev (B*M) or NULL*/, void *stream);
 
+/* cqt / vqt (cqt.py; the filter bank of librosa 0.10's cqt / vqt in direct form).  y: (B, L) float32; taps: the n_bins
+ * complex filters back to back as (re, im) pairs, filter k at taps[tap_offset[k] .. tap_offset[k+1]), its first tap at
+ * position m0[k] relative to the frame's centre; T = 1 + L / hop (AP_ERR_INVALID otherwise).
+ *   C[b,k,t] = scale[k] sum_{j < L_k} ypad[b, t hop + m0[k] + j] conj(taps[tap_offset[k] + j]),  L_k = tap_offset[k+1] - tap_offset[k]
+ *   ypad: y outside [0, L) by pad_mode (AP_PAD_CONSTANT, AP_PAD_EDGE, AP_PAD_REFLECT: NumPy's "reflect" at any distance),
+ *   computed on load.
+ * out: (B, n_bins, T) complex64 as (re, im) pairs, rows out_row_stride complex values apart (>= T; the padding is never
+ * written).  tap_offset, m0, scale and taps are device arrays; the caller keeps 0 <= L_k <= ap_cqt_max_taps() and
+ * |m0[k]| <= ap_cqt_max_taps().  One launch; every product is a fused multiply-add and every sum has a fixed order
+ * (csrc/kernels_cqt.h).  AP_ERR_INVALID: sizes, hop, pad_mode, T, the stride; AP_ERR_UNSUPPORTED: L > 2^30. */
+int ap_cqt_max_taps(void);
+int ap_cqt_f32(const float *y /*dev*/, int64_t B, int64_t L, int hop, int pad_mode, const float *taps /*dev, float2*/,
+               const int64_t *tap_offset /*dev (n_bins+1)*/, const int32_t *m0 /*dev (n_bins)*/,
+               const float *scale /*dev (n_bins)*/, int n_bins, int64_t T, float *out /*dev*/, int64_t out_row_stride,
+               void *stream);
+
 #ifdef __cplusplus
 }
 #endif
