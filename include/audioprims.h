@@ -690,6 +690,30 @@ int ap_cqt_f32(const float *y /*dev*/, int64_t B, int64_t L, int hop, int pad_mo
                const float *scale /*dev (n_bins)*/, int n_bins, int64_t T, float *out /*dev*/, int64_t out_row_stride,
                void *stream);
 
+/* chroma_stft / chroma_cqt / tonnetz (chroma.py): fold a spectrum onto n_out rows, threshold and normalise, one pass.
+ * x: (B, K, T), rows in_row_stride elements apart (>= T), clips K rows apart; in_kind 0: float32, v = x; 1: complex64
+ * as (re, im), v = |z|; 2: complex64, v = re^2 + im^2.  w: (n_out, K) row-major on the device, or NULL for the identity
+ * (then K == n_out).  Per frame, in this order:
+ *   a_c = sum_k w[c,k] v_k;  pre_l1: a_c /= max(sum_k |v_k|, -> 1 below FLT_MIN);  use_threshold: a_c < threshold -> 0;
+ *   norm 0: none, 1: sum |a|, 2: sqrt(sum a^2), 3: max |a|, a norm below FLT_MIN counts as 1;  out_c = a_c / norm.
+ * out: (B, n_out, T) float32, rows out_row_stride apart (>= T; the padding is never written).  One read of x, one write
+ * of out; every product is a fused multiply-add, every sum has a fixed order, sqrt and / are IEEE (csrc/kernels_chroma.h):
+ * a frame's bits do not depend on the batch.  A NaN stays in its frame.  AP_ERR_INVALID: NULL x / out, sizes, n_out above
+ * ap_chroma_max_out(), a stride below T, an unknown in_kind or norm, w == NULL with K != n_out. */
+int ap_chroma_max_out(void);
+int ap_chroma_fold_f32(const float *x /*dev*/, int in_kind, int64_t B, int K, int64_t T, int64_t in_row_stride,
+                       const float *w /*dev (n_out*K) or NULL*/, int n_out, int pre_l1, int use_threshold, float threshold,
+                       int norm, float *out /*dev*/, int64_t out_row_stride, void *stream);
+
+/* chroma_cens (chroma.py): chroma (B, n, T) float32, rows in_row_stride apart.  Per frame: L1-normalise (rule above),
+ * quantise q = 0.25 ([v > 0.4] + [v > 0.2] + [v > 0.1] + [v > 0.05]); along time, when n_taps > 0,
+ * s[t] = sum_j taps[j] q[t + (n_taps - 1) / 2 - j] with q = 0 outside [0, T) (SciPy's "same"); then normalise by `norm`
+ * as above.  One launch, the quantised values stay in LDS.  n <= ap_chroma_max_out(), n_taps <= ap_chroma_max_smooth(). */
+int ap_chroma_max_smooth(void);
+int ap_chroma_cens_f32(const float *chroma /*dev*/, int64_t B, int n, int64_t T, int64_t in_row_stride,
+                       const float *taps /*dev (n_taps) or NULL*/, int n_taps, int norm, float *out /*dev*/,
+                       int64_t out_row_stride, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

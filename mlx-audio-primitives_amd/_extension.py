@@ -64,6 +64,7 @@ ABI_SYMBOLS = [
     "ap_beat_track_max_frames", "ap_beat_track_max_period", "ap_beat_track_f32",
     "ap_pcen_f32",
     "ap_cqt_max_taps", "ap_cqt_f32",
+    "ap_chroma_max_out", "ap_chroma_fold_f32", "ap_chroma_max_smooth", "ap_chroma_cens_f32",
     "ap_pcm16_to_f32", "ap_melspec_pcm16_fused", "ap_melspec_pcm16_f32",
 ]
 
@@ -151,6 +152,10 @@ def _declare(lib) -> None:
         "ap_pcen_f32": [P, L, L, L, L, P, L, I, ctypes.c_double, F, F, F, F, P, P, L, P, P],
         "ap_cqt_max_taps": [],
         "ap_cqt_f32": [P, L, L, I, I, P, P, P, P, I, L, P, L, P],
+        "ap_chroma_max_out": [],
+        "ap_chroma_fold_f32": [P, I, L, I, L, L, P, I, I, I, F, I, P, L, P],
+        "ap_chroma_max_smooth": [],
+        "ap_chroma_cens_f32": [P, L, I, L, L, P, I, I, P, L, P],
         "ap_pcm16_to_f32": [P, L, F, P, P],
         "ap_melspec_pcm16_fused": [L, I, I, I, I, I, F, P],
         "ap_melspec_pcm16_f32": [P, L, L, I, I, P, P, I, I, L, P, P, P, I, F, P, P, P, P],
