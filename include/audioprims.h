@@ -714,6 +714,40 @@ int ap_chroma_cens_f32(const float *chroma /*dev*/, int64_t B, int n, int64_t T,
                        const float *taps /*dev (n_taps) or NULL*/, int n_taps, int norm, float *out /*dev*/,
                        int64_t out_row_stride, void *stream);
 
+/* dtw / dtw_backtracking (dtw.py): dynamic time warping, the definition of DESIGN.md 9.9 (csrc/kernels_dtw.h).
+ * Caps: d <= ap_dtw_max_features(), n_steps <= ap_dtw_max_steps(), a step's components <= ap_dtw_max_step(),
+ * N, M <= ap_dtw_max_len().  AP_ERR_INVALID: NULL buffers, empty sizes, a stride below the row length, an unknown metric,
+ * a step with a negative component or (0, 0); AP_ERR_UNSUPPORTED: a size or a step component above its cap.
+ *
+ * ap_dtw_cost_f32: X (B, d, N) and Y (B, d, M) float32, rows x_row_stride / y_row_stride apart, pairs d rows apart;
+ * C (B, N, M), rows c_row_stride apart.  metric 0: sqrt(sum (x - y)^2), 1: sum (x - y)^2, 2: sum |x - y|,
+ * 3: 1 - x.y / (|x| |y|) with a product of norms below FLT_MIN counted as 1.  Features summed in ascending order.
+ *
+ * ap_dtw_accumulate_f32: steps_ab (host, n_steps pairs (a, b)), weights_add / weights_mul (host, n_steps), taken by
+ * value.  use_band: cells with not (-band_r - max(N - M, 0) < j - i < band_r + max(M - N, 0)) cost +inf (a predicate,
+ * C is not copied).  D (B, N, M) float32 and steps (B, N, M) uint8 (the winning step, 254: the path starts here, 255:
+ * unreachable), rows d_row_stride / steps_row_stride apart.  One launch per tile-anti-diagonal on `stream`.  Every
+ * addition and multiplication is rounded on its own and the comparison is the strict <: the bits of D and steps depend
+ * on nothing but C and the arguments.  Nothing outside the N x M payload of a row is read or written.
+ *
+ * ap_dtw_backtrack_i32: follows steps from (N - 1, j0) until a cell with code 254; j0 = start[b] when start is given,
+ * else the first minimum of D's last row when subseq (D may be NULL otherwise), else M - 1.  path (B, N + M - 1, 2)
+ * int32 holds (i, j) from the end of the path to its start, len (B) the number of cells or -1 when there is no path. */
+int ap_dtw_max_features(void);
+int ap_dtw_max_steps(void);
+int ap_dtw_max_step(void);
+int ap_dtw_max_len(void);
+int ap_dtw_cost_f32(const float *X /*dev*/, const float *Y /*dev*/, int64_t B, int d, int64_t N, int64_t M, int64_t x_row_stride,
+                    int64_t y_row_stride, int metric, float *C /*dev*/, int64_t c_row_stride, void *stream);
+int ap_dtw_accumulate_f32(const float *C /*dev*/, int64_t B, int64_t N, int64_t M, int64_t c_row_stride, int n_steps,
+                          const int32_t *steps_ab /*host (2 n_steps)*/, const float *weights_add /*host*/,
+                          const float *weights_mul /*host*/, int subseq, int use_band, int64_t band_r, float *D /*dev*/,
+                          int64_t d_row_stride, uint8_t *steps /*dev*/, int64_t steps_row_stride, void *stream);
+int ap_dtw_backtrack_i32(const float *D /*dev or NULL*/, const uint8_t *steps /*dev*/, const int32_t *start /*dev (B) or NULL*/,
+                         int64_t B, int64_t N, int64_t M, int64_t d_row_stride, int64_t steps_row_stride, int n_steps,
+                         const int32_t *steps_ab /*host (2 n_steps)*/, int subseq, int32_t *path /*dev*/, int32_t *len /*dev*/,
+                         void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,6 +10,7 @@ from ._validation import validate_non_negative, validate_positive, validate_rang
 from .convert import amplitude_to_db, db_to_amplitude, db_to_power, power_to_db
 from .chroma import chroma_cens, chroma_cqt, chroma_filterbank, chroma_stft, cq_to_chroma, tonnetz
 from .cqt import cqt, cqt_frequencies, vqt
+from .dtw import dtw, dtw_backtracking
 from .decompose import harmonic, hpss, hpss_audio, hpss_medians, percussive
 from .features import (spectral_bandwidth, spectral_centroid, spectral_contrast, spectral_features, spectral_flatness,
                        spectral_rolloff, zero_crossing_rate)
@@ -38,7 +39,7 @@ __all__ = [
     "griffinlim", "griffinlim_iter", "resample", "resample_poly",
     "set_spectrum_layout", "stft_padded_rows",
     "spectral_centroid", "spectral_bandwidth", "spectral_rolloff", "spectral_flatness", "spectral_contrast", "spectral_features",
-    "StreamingSTFT", "StreamingISTFT", "autocorrelation", "pitch_detect_acf", "periodicity", "yin", "yin_cmnd", "hpss", "hpss_medians", "hpss_audio", "harmonic", "percussive", "onset_strength", "onset_detect", "peak_pick", "tempogram", "tempo", "tempo_frequencies", "beat_track", "pcen", "StreamingPCEN", "cqt", "vqt", "cqt_frequencies", "chroma_stft", "chroma_cqt", "chroma_cens", "tonnetz", "chroma_filterbank", "cq_to_chroma", "pcm16_to_float", "hz_to_bark", "bark_to_hz", "bark_filterbank", "linear_filterbank", "filterbank_spectrogram",
+    "StreamingSTFT", "StreamingISTFT", "autocorrelation", "pitch_detect_acf", "periodicity", "yin", "yin_cmnd", "hpss", "hpss_medians", "hpss_audio", "harmonic", "percussive", "onset_strength", "onset_detect", "peak_pick", "tempogram", "tempo", "tempo_frequencies", "beat_track", "pcen", "StreamingPCEN", "cqt", "vqt", "cqt_frequencies", "chroma_stft", "chroma_cqt", "chroma_cens", "tonnetz", "chroma_filterbank", "cq_to_chroma", "dtw", "dtw_backtracking", "pcm16_to_float", "hz_to_bark", "bark_to_hz", "bark_filterbank", "linear_filterbank", "filterbank_spectrogram",
     "zero_crossing_rate", "frame", "rms", "preemphasis", "deemphasis", "delta",
     "mfcc", "dct", "power_to_db", "db_to_power", "amplitude_to_db", "db_to_amplitude",
     "validate_positive", "validate_non_negative", "validate_range",

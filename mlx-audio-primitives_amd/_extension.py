@@ -65,6 +65,8 @@ ABI_SYMBOLS = [
     "ap_pcen_f32",
     "ap_cqt_max_taps", "ap_cqt_f32",
     "ap_chroma_max_out", "ap_chroma_fold_f32", "ap_chroma_max_smooth", "ap_chroma_cens_f32",
+    "ap_dtw_max_features", "ap_dtw_max_steps", "ap_dtw_max_step", "ap_dtw_max_len",
+    "ap_dtw_cost_f32", "ap_dtw_accumulate_f32", "ap_dtw_backtrack_i32",
     "ap_pcm16_to_f32", "ap_melspec_pcm16_fused", "ap_melspec_pcm16_f32",
 ]
 
@@ -156,6 +158,13 @@ def _declare(lib) -> None:
         "ap_chroma_fold_f32": [P, I, L, I, L, L, P, I, I, I, F, I, P, L, P],
         "ap_chroma_max_smooth": [],
         "ap_chroma_cens_f32": [P, L, I, L, L, P, I, I, P, L, P],
+        "ap_dtw_max_features": [],
+        "ap_dtw_max_steps": [],
+        "ap_dtw_max_step": [],
+        "ap_dtw_max_len": [],
+        "ap_dtw_cost_f32": [P, P, L, I, L, L, L, L, I, P, L, P],
+        "ap_dtw_accumulate_f32": [P, L, L, L, L, I, P, P, P, I, I, L, P, L, P, L, P],
+        "ap_dtw_backtrack_i32": [P, P, P, L, L, L, L, L, I, P, I, P, P, P],
         "ap_pcm16_to_f32": [P, L, F, P, P],
         "ap_melspec_pcm16_fused": [L, I, I, I, I, I, F, P],
         "ap_melspec_pcm16_f32": [P, L, L, I, I, P, P, I, I, L, P, P, P, I, F, P, P, P, P],
