@@ -12,12 +12,16 @@
 #define APW_X_COMPLEX 1284   // complex slots of one wave's exchange buffer (>= APW_T1(63)+16, >= zidx(1023)+1)
 #define APW_PASSES 4          // contraction passes whose part descriptors live in registers (256 parts)
 #define APW_TW2_COMPLEX 72   // 4 rows x 17 (padded) of W_64^(a*c), rounded to 16 bytes
-// run kernels (kernels_mel2048.h): both twiddle tables as rows of 18 complex = 144 bytes, entries 0..15 used
-// (entry 0 is W^0), so that a lane reads its 15 twiddles as eight aligned ds_read_b128; the row stride is
-// 4 * 9 dwords, 9 odd: the 16 lanes of every ds_read_b128 lane group fall on 16 different 4-bank sets
+// run kernels (kernels_mel2048.h): both twiddle tables as one row per lane, read as aligned ds_read_b128.
+// The twiddles are applied on the READ side of the two exchanges, folded into the butterflies that follow
+// (apm_fill_tables).  Table 1: rows of 18 complex = 144 bytes, entries 0..15 used, eight reads; table 2:
+// rows of 14 complex = 112 bytes, entries 0..11 used, six reads.  The row strides are 4 * 9 and 4 * 7
+// dwords, 9 and 7 odd: the 16 lanes of every ds_read_b128 lane group fall on 16 different 4-bank sets
+// (tools/lds_banks.py).
 #define APM_TW_ROW 18
-#define APM_TW1_COMPLEX (64 * APM_TW_ROW)   // W_1024^(lane k), one row per lane
-#define APM_TW2_COMPLEX (4 * APM_TW_ROW)    // W_64^(a c), one row per a = lane & 3
+#define APM_TW2_ROW 14
+#define APM_TW1_COMPLEX (64 * APM_TW_ROW)   // W_1024^((4 i + a) k) of the reading lane 4 k + a, i = 0..15
+#define APM_TW2_COMPLEX (64 * APM_TW2_ROW)  // W_64^(a c) of the lane's four radix-4 groups, a = 1..3
 
 struct ApMelWaveParams {
     const float *y;            // (B, L)

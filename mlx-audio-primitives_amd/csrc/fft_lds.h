@@ -240,6 +240,115 @@ AP_DEV void ap_fft4_weighted(const ap_float2 &x0, const ap_float2 &w0, const ap_
     a3 = ap_sub_mi(t1, e);
 }
 
+// ---- twiddles folded into the butterfly level that consumes them ----------------------
+// A twiddle multiply followed by the sum and the difference with another value costs 2 + 2 packed
+// instructions when it is issued as a complex multiply of its own; the forms below take the products as
+// FMA addends.  Every form is a fixed chain of FMAs: the scalar twins (AP_HOST_EMU) spell the same chain
+// with fmaf, in the same order.
+//   compile-time twiddle w = c (1 - i t), t = tan of its angle:  u = b - i t b is one FMA and a +- c u
+//   one each: 3 for 4 (one input twiddled), u_a, u_b, c_a u_a, +- c_b u_b: 5 for 6 (both twiddled);
+//   table twiddle (c, s), any angle: a' = w_a a (2), s = a' + w_b b as a chain of two FMAs, and the
+//   difference d = 2 a' - s as one FMA with the inline constant 2.0: 5 for 6, or 3 for 4 with a' = a.
+//   d carries one rounding more than a' - w_b b would: of the size of the sum's own.
+#ifdef AP_PACKED_COMPLEX
+// b (1 - i t) = (b.x + t b.y, b.y - t b.x)
+AP_DEV ap_float2 ap_rot_c(ap_float2 b, float t) { return __builtin_elementwise_fma(b.yx, ap_mk(t, -t), b); }
+// 2 a - s
+AP_DEV ap_float2 ap_twice_minus(ap_float2 a, ap_float2 s) { return __builtin_elementwise_fma(a, ap_mk(2.0f, 2.0f), -s); }
+// a + w b, the two FMAs of the product taking a as their addend
+AP_DEV ap_float2 ap_fma_fw(ap_float2 b, ap_float2 w, ap_float2 a) {
+    return ap_cmul_tail_fw(b, w, __builtin_elementwise_fma(b, w.xx, a));
+}
+// u c + a
+AP_DEV ap_float2 ap_fma_sc(ap_float2 u, float c, ap_float2 a) { return ap_fma_s(u, c, a); }
+#else
+AP_DEV ap_float2 ap_rot_c(ap_float2 b, float t) { return ap_mk(fmaf(b.y, t, b.x), fmaf(b.x, -t, b.y)); }
+AP_DEV ap_float2 ap_twice_minus(ap_float2 a, ap_float2 s) { return ap_mk(fmaf(a.x, 2.0f, -s.x), fmaf(a.y, 2.0f, -s.y)); }
+AP_DEV ap_float2 ap_fma_fw(ap_float2 b, ap_float2 w, ap_float2 a) {
+    const float x = fmaf(b.x, w.x, a.x), y = fmaf(b.y, w.x, a.y);
+    return ap_mk(fmaf(b.y, w.y, x), fmaf(-b.x, w.y, y));
+}
+AP_DEV ap_float2 ap_fma_sc(ap_float2 u, float c, ap_float2 a) { return ap_mk(fmaf(u.x, c, a.x), fmaf(u.y, c, a.y)); }
+#endif
+// a w with the roundings of the packed ap_mul_fw (a product, then one FMA) in both builds
+AP_DEV ap_float2 ap_mul_fw_chain(ap_float2 a, ap_float2 w) {
+#ifdef AP_PACKED_COMPLEX
+    return ap_mul_fw(a, w);
+#else
+    return ap_mk(fmaf(a.y, w.y, a.x * w.x), fmaf(-a.x, w.y, a.y * w.x));
+#endif
+}
+// s = a + w b, d = a - w b with w = c (1 - i t): 3 instructions
+AP_DEV void ap_sumdiff_c1(ap_float2 a, ap_float2 b, float c, float t, ap_float2 &s, ap_float2 &d) {
+    const ap_float2 u = ap_rot_c(b, t);
+    s = ap_fma_sc(u, c, a);
+    d = ap_fma_sc(u, -c, a);
+}
+// s = wa a + wb b, d = wa a - wb b with wa = ca (1 - i ta), wb = cb (1 - i tb): 5 instructions
+AP_DEV void ap_sumdiff_c2(ap_float2 a, float ca, float ta, ap_float2 b, float cb, float tb, ap_float2 &s,
+                          ap_float2 &d) {
+    const ap_float2 ua = ap_rot_c(a, ta), ub = ap_rot_c(b, tb);
+    const ap_float2 m = ap_scale(ua, ca);
+    s = ap_fma_sc(ub, cb, m);
+    d = ap_fma_sc(ub, -cb, m);
+}
+// s = a + w b, d = a - w b, w a forward table twiddle (c, s): 3 instructions
+AP_DEV void ap_sumdiff_w1(ap_float2 a, ap_float2 b, ap_float2 w, ap_float2 &s, ap_float2 &d) {
+    s = ap_fma_fw(b, w, a);
+    d = ap_twice_minus(a, s);
+}
+// s = wa a + wb b, d = wa a - wb b, both forward table twiddles: 5 instructions
+AP_DEV void ap_sumdiff_w2(ap_float2 a, ap_float2 wa, ap_float2 b, ap_float2 wb, ap_float2 &s, ap_float2 &d) {
+    const ap_float2 m = ap_mul_fw_chain(a, wa);
+    s = ap_fma_fw(b, wb, m);
+    d = ap_twice_minus(m, s);
+}
+// radix-4 butterfly of x_i w_i, forward table twiddles on all four inputs: 14 instructions for 16 + 8
+AP_DEV void ap_fft4_twiddled(const ap_float2 &x0, const ap_float2 &w0, const ap_float2 &x1, const ap_float2 &w1,
+                             const ap_float2 &x2, const ap_float2 &w2, const ap_float2 &x3, const ap_float2 &w3,
+                             ap_float2 &a0, ap_float2 &a1, ap_float2 &a2, ap_float2 &a3) {
+    ap_float2 t0, t1, t2, e;
+    ap_sumdiff_w2(x0, w0, x2, w2, t0, t1);
+    ap_sumdiff_w2(x1, w1, x3, w3, t2, e);
+    a0 = ap_add(t0, t2);
+    a2 = ap_sub(t0, t2);
+    a1 = ap_add_mi(t1, e);
+    a3 = ap_sub_mi(t1, e);
+}
+// the same with input 0 untwiddled, in place: 12 instructions for 12 + 8
+AP_DEV void ap_fft4_twiddled3(ap_float2 &a0, ap_float2 &a1, const ap_float2 &w1, ap_float2 &a2, const ap_float2 &w2,
+                              ap_float2 &a3, const ap_float2 &w3) {
+    ap_float2 t0, t1, t2, e;
+    ap_sumdiff_w1(a0, a2, w2, t0, t1);
+    ap_sumdiff_w2(a1, w1, a3, w3, t2, e);
+    a0 = ap_add(t0, t2);
+    a2 = ap_sub(t0, t2);
+    a1 = ap_add_mi(t1, e);
+    a3 = ap_sub_mi(t1, e);
+}
+// radix-4 butterfly of (a0, w1 a1, w2 a2, w3 a3), compile-time twiddles w_i = c_i (1 - i t_i): 12 for 12 + 8
+AP_DEV void ap_fft4_c(ap_float2 &a0, ap_float2 &a1, ap_float2 &a2, ap_float2 &a3, float c1, float t1c, float c2,
+                      float t2c, float c3, float t3c) {
+    ap_float2 t0, t1, t2, e;
+    ap_sumdiff_c1(a0, a2, c2, t2c, t0, t1);
+    ap_sumdiff_c2(a1, c1, t1c, a3, c3, t3c, t2, e);
+    a0 = ap_add(t0, t2);
+    a2 = ap_sub(t0, t2);
+    a1 = ap_add_mi(t1, e);
+    a3 = ap_sub_mi(t1, e);
+}
+// the same with w2 = -i (as ap_fft4_a2mi): 11 for 8 + 8
+AP_DEV void ap_fft4_c_a2mi(ap_float2 &a0, ap_float2 &a1, ap_float2 &a2, ap_float2 &a3, float c1, float t1c, float c3,
+                           float t3c) {
+    ap_float2 t2, e;
+    const ap_float2 t0 = ap_add_mi(a0, a2), t1 = ap_sub_mi(a0, a2);
+    ap_sumdiff_c2(a1, c1, t1c, a3, c3, t3c, t2, e);
+    a0 = ap_add(t0, t2);
+    a2 = ap_sub(t0, t2);
+    a1 = ap_add_mi(t1, e);
+    a3 = ap_sub_mi(t1, e);
+}
+
 template <>
 struct ApButterfly<16> {
     static AP_DEV void run(ap_float2 *v) {
@@ -280,6 +389,42 @@ struct ApButterfly<16> {
         for (int p = 0; p < 4; ++p) {
             if (p == 2) ap_fft4_a2mi(a[0][p], a[1][p], a[2][p], a[3][p]);
             else ap_fft4(a[0][p], a[1][p], a[2][p], a[3][p]);
+            v[p] = a[0][p]; v[p + 4] = a[1][p]; v[p + 8] = a[2][p]; v[p + 12] = a[3][p];
+        }
+    }
+    // run_weighted / run with the W16 twiddles folded into the second level (finish_fused)
+    static AP_DEV void run_weighted_fused(const ap_float2 *x, const ap_float2 *w, ap_float2 *v) {
+        ap_float2 a[4][4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            ap_fft4_weighted(x[r], w[r], x[r + 4], w[r + 4], x[r + 8], w[r + 8], x[r + 12], w[r + 12],
+                             a[r][0], a[r][1], a[r][2], a[r][3]);
+        finish_fused(a, v);
+    }
+    // v = DFT16 of (x[i] t[i]), t[i] forward table twiddles folded into the first level (x may be v)
+    static AP_DEV void run_twiddled_fused(const ap_float2 *x, const ap_float2 *t, ap_float2 *v) {
+        ap_float2 a[4][4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            ap_fft4_twiddled(x[r], t[r], x[r + 4], t[r + 4], x[r + 8], t[r + 8], x[r + 12], t[r + 12],
+                             a[r][0], a[r][1], a[r][2], a[r][3]);
+        finish_fused(a, v);
+    }
+    // finish with W16^(r p) = c (1 - i t) taken inside the radix-4 over r: 43 packed instructions for the
+    // 16 + 32 of finish (p = 1, 3: 12 for 14, p = 2: 11 for 12)
+    static AP_DEV void finish_fused(ap_float2 (&a)[4][4], ap_float2 *v) {
+        const float C1 = 0.92387953251128675613f, S1 = 0.38268343236508977173f;
+        const float H = 0.70710678118654752440f;
+        const float T1 = 0.41421356237309504880f, T3 = 2.41421356237309504880f;   // tan(pi / 8), tan(3 pi / 8)
+        ap_fft4(a[0][0], a[1][0], a[2][0], a[3][0]);
+        // p = 1: W16^1 = (C1, S1), W16^2 = (H, H), W16^3 = (S1, C1)
+        ap_fft4_c(a[0][1], a[1][1], a[2][1], a[3][1], C1, T1, H, 1.0f, S1, T3);
+        // p = 2: W16^2 = (H, H), W16^4 = -i, W16^6 = (-H, H)
+        ap_fft4_c_a2mi(a[0][2], a[1][2], a[2][2], a[3][2], H, 1.0f, -H, -1.0f);
+        // p = 3: W16^3 = (S1, C1), W16^6 = (-H, H), W16^9 = (-C1, -S1)
+        ap_fft4_c(a[0][3], a[1][3], a[2][3], a[3][3], S1, T3, -H, -1.0f, -C1, T1);
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
             v[p] = a[0][p]; v[p + 4] = a[1][p]; v[p + 8] = a[2][p]; v[p + 12] = a[3][p];
         }
     }

@@ -22,8 +22,12 @@
 //     the paired real split take the lane's 16 bins without another LDS round trip - 32 packed adds
 //     and 8 selects instead of the 64 v_fmac_f32_dpp, 32 v_cndmask and the s_nop pads of the DPP
 //     quad stage (apm_quad8), and 8 ds_read_b128 instead of 17 ds_read_b64 for the split;
-//   * the two twiddle tables are rows of 18 complex per lane (apm_fill_tables): eight aligned
-//     ds_read_b128 per table and frame instead of 15 paired 8-byte reads at half the LDS rate;
+//   * the two twiddle tables are one row per lane (apm_fill_tables): eight and six aligned
+//     ds_read_b128 per frame instead of 15 paired 8-byte reads each at half the LDS rate;
+//   * no twiddle is a complex multiply of its own: the W16 constants inside both radix-16s, the W_1024
+//     twiddles (applied by the lane that READS exchange #1) and the W_64 twiddles (read side of exchange
+//     #2, none for input a = 0) are FMA addends of the butterfly level that consumes them (fft_lds.h,
+//     "twiddles folded into the butterfly"): 30 packed instructions fewer per frame;
 //   * the 8-frame output run of a lane's two mel rows lives in registers (32 contiguous bytes per
 //     row and lane, as in ap_mel1024_wave_kernel): no output tile in LDS; the partial sums
 //     alias the idle upper half of the wave's exchange buffer.
@@ -43,8 +47,8 @@
 // re-read from LDS every frame (bit mask; 8 waves per CU leave 256 VGPRs per lane).  The product
 // uses APM_REGS: with the two twiddle tables as well hipcc's scheduler spills inside the frame loop.
 #define APM_REG_WIN 1         // window pairs                 32 VGPRs, saves 16 ds_read_b64 per frame
-#define APM_REG_TW1 2         // W_1024^(lane k1)             30 VGPRs, saves 15
-#define APM_REG_TW2 4         // W_64^(a c)                   30 VGPRs, saves 15
+#define APM_REG_TW1 2         // W_1024^((4 i + a) k) row     32 VGPRs, saves 8 ds_read_b128
+#define APM_REG_TW2 4         // W_64^(a c) of the 4 groups   24 VGPRs, saves 6 ds_read_b128
 #define APM_REG_SPLIT 8       // W_2048^k / 2 of the 8 split pairs, 16 VGPRs (always in registers: apm_split;
                               // the bit stays in APM_REGS so that the instantiations keep their names)
 #define APM_REGS (APM_REG_WIN | APM_REG_SPLIT)
@@ -69,7 +73,7 @@ struct ApmPairLane {
 
 AP_DEV ApmPairLane apm_pair_lane_init(int lane) {
     ApmPairLane p;
-    p.L = (int)((0xE311825200ull >> (5 * ((lane >> 2) & 7))) & 31) + (lane & 3) + (lane & 32);  // 0,16,20,4,24,8,12,28
+    p.L = apm_lane_index(lane);                    // 0,16,20,4,24,8,12,28 (kernels_wave.h)
     p.l0 = p.L == 0;
     p.lp = p.l0 ? 128 : p.L;
     p.rd[0] = apm_gidx(p.L);
@@ -79,28 +83,33 @@ AP_DEV ApmPairLane apm_pair_lane_init(int lane) {
     return p;
 }
 
-// forward transform of apw_forward up to the W_64 twiddles; the last radix-4 is left to apm_split,
-// the exchange hands it whole groups.  tw1row / tw2row: the lane's rows of the two twiddle tables in the
-// 18-complex layout of apm_fill_tables (W_1024^(lane k) and plain W_64^(a c)), 16-byte aligned: eight
-// ds_read_b128 each (entry 0 = W^0 is read and not used).
+// forward transform of apw_forward up to exchange #2; the W_64 twiddles and the last radix-4 are left to
+// apm_split, the exchange hands it whole groups.  Both twiddle multiplies ride on the butterfly level that
+// consumes them (fft_lds.h): the values cross the exchanges untwiddled, the reading lane 4 k + a takes
+// W_1024^((4 i + a) k) of element i into the first level of the second radix-16 (8 pairs of 5 instructions
+// for 30 + 16), and the W16 twiddles inside both radix-16s sit in their second levels (finish_fused).
+// tw1row / tw2row: the lane's rows of the two twiddle tables (apm_fill_tables), 16-byte aligned: eight and six
+// ds_read_b128.  t2: the lane's W_64 twiddles for apm_split, read here ahead of the stores of exchange #2
+// (with the reads of exchange #1, live across the second radix-16, three instantiations spilled).
 #ifdef AP_PACKED_COMPLEX
-// (as vector loads: read through the ap_float4 struct the four floats become a chain of scalar loads, and with
-// entry 0 dead the chain starts 8 bytes into the row and comes out as 8-byte pairs again)
+// (as vector loads: read through the ap_float4 struct the four floats become a chain of scalar loads)
 typedef float apm_float4v __attribute__((ext_vector_type(4)));
-AP_DEV void apm_load_row(const ap_float2 *row, ap_float2 (&t)[16]) {
+template <int N>
+AP_DEV void apm_load_row(const ap_float2 *row, ap_float2 (&t)[N]) {
     const apm_float4v *src = reinterpret_cast<const apm_float4v *>(row);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
+    for (int j = 0; j < N / 2; ++j) {
         const apm_float4v v = src[j];
         t[2 * j] = __builtin_shufflevector(v, v, 0, 1);
         t[2 * j + 1] = __builtin_shufflevector(v, v, 2, 3);
     }
 }
 #else
-AP_DEV void apm_load_row(const ap_float2 *row, ap_float2 (&t)[16]) {
+template <int N>
+AP_DEV void apm_load_row(const ap_float2 *row, ap_float2 (&t)[N]) {
     const ap_float4 *src = reinterpret_cast<const ap_float4 *>(row);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
+    for (int j = 0; j < N / 2; ++j) {
         const ap_float4 v = src[j];
         t[2 * j] = ap_mk(v.x, v.y);
         t[2 * j + 1] = ap_mk(v.z, v.w);
@@ -110,35 +119,33 @@ AP_DEV void apm_load_row(const ap_float2 *row, ap_float2 (&t)[16]) {
 // (the samples x and the window pairs w go in separately: the window rides on the first butterfly level)
 template <int REGS>
 AP_DEV void apm_forward(const ap_float2 (&x)[16], const ap_float2 (&w)[16], ap_float2 *X, const ap_float2 *tw1row,
-                        const ap_float2 *tw2row, const ap_float2 (&t1r)[16], const ap_float2 (&t2r)[16],
-                        const ApwLane &c) {
+                        const ap_float2 *tw2row, const ap_float2 (&t1r)[16], const ap_float2 (&t2r)[12],
+                        ap_float2 (&t2)[12], const ApwLane &c) {
     const int lane = c.lane;
-    ap_float2 v[16];
+    ap_float2 v[16], t1[16];
     if (REGS & APM_REG_TW1) {
-        ApButterfly<16>::run_weighted(x, w, v);
 #pragma unroll
-        for (int k = 1; k < 16; ++k) v[k] = ap_mul_fw(v[k], t1r[k]);
+        for (int i = 0; i < 16; ++i) t1[i] = t1r[i];
     } else {
-        ap_float2 t1[16];
         apm_load_row(tw1row, t1);
-        ApButterfly<16>::run_weighted(x, w, v);
-#pragma unroll
-        for (int k = 1; k < 16; ++k) v[k] = ap_mul_fw(v[k], t1[k]);
     }
+    ApButterfly<16>::run_weighted_fused(x, w, v);
     {
         const int a = lane & 3, bq = lane >> 2;
 #pragma unroll
         for (int k = 0; k < 16; ++k) X[APW_T1(k * 4 + a) + bq] = v[k];
     }
     AP_WAVE_SYNC();
-    ap_float2 t2[16];
 #pragma unroll
     for (int i = 0; i < 16; ++i) v[i] = X[APW_T1(lane) + i];
-    if (!(REGS & APM_REG_TW2)) apm_load_row(tw2row, t2);
     AP_WAVE_SYNC();
-    ApButterfly<16>::run(v);
+    ApButterfly<16>::run_twiddled_fused(v, t1, v);
+    if (REGS & APM_REG_TW2) {
 #pragma unroll
-    for (int cc = 1; cc < 16; ++cc) v[cc] = ap_mul_fw(v[cc], (REGS & APM_REG_TW2) ? t2r[cc] : t2[cc]);
+        for (int i = 0; i < 12; ++i) t2[i] = t2r[i];
+    } else {
+        apm_load_row(tw2row, t2);
+    }
     // exchange #2: v[cc] is input a = lane & 3 of group k1 + 16 cc (apm_gidx(k1 + 16 cc) = apm_gidx(k1) + 68 cc)
     const int wb = apm_gidx(c.k1p) + (lane & 3);
 #pragma unroll
@@ -146,9 +153,10 @@ AP_DEV void apm_forward(const ap_float2 (&x)[16], const ap_float2 (&w)[16], ap_f
     AP_WAVE_SYNC();
 }
 
-// The lane's four groups out of the exchange, their radix-4s (ap_fft4: the same additions, in the same
-// order, as the DPP quad stage of apw_forward) and the eight paired real splits of apw_split, all in
-// registers; |X|^p of the 16 bins (and bin 512 on lane L = 0) into the plane pp, which aliases X.
+// The lane's four groups out of the exchange, their radix-4s with the W_64^(a c) twiddles of the inputs
+// a = 1..3 folded into the first level (ap_fft4_twiddled3: 12 instructions a group for 6 + 8; t2[3 s + a - 1],
+// row of apm_fill_tables) and the eight paired real splits of apw_split, all in registers; |X|^p of the 16
+// bins (and bin 512 on lane L = 0) into the plane pp, which aliases X.
 // wsp[i]: W_2048^k / 2 of pair i (apm_split_twiddles).
 //   pair   0      1        2         3         4         5         6         7
 //   k      L      L + 256  512 - lp  256 - lp  L + 64    L + 320   448 - L   192 - L
@@ -166,7 +174,7 @@ AP_DEV void apm_split_twiddles(const ApmPairLane &p, const ap_float2 *tw, ap_flo
 
 template <int PMODE>
 AP_DEV void apm_split(const ap_float2 *X, float *pp, const ApmPairLane &p, const ap_float2 (&wsp)[8],
-                      const ApwLane &c, float power) {
+                      const ap_float2 (&t2)[12], const ApwLane &c, float power) {
     ap_float2 z[4][4];                    // z[s][q] = Z[g_s + 256 q] after the radix-4s
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
@@ -177,7 +185,8 @@ AP_DEV void apm_split(const ap_float2 *X, float *pp, const ApmPairLane &p, const
     }
     AP_WAVE_SYNC();
 #pragma unroll
-    for (int s = 0; s < 4; ++s) ap_fft4(z[s][0], z[s][1], z[s][2], z[s][3]);
+    for (int s = 0; s < 4; ++s)
+        ap_fft4_twiddled3(z[s][0], z[s][1], t2[3 * s], z[s][2], t2[3 * s + 1], z[s][3], t2[3 * s + 2]);
     // (Z[k], Z[1024 - k]) of the eight pairs; L = 0: (Z0, Z0), (Z256, Z768), (Z384, Z640), (Z128, Z896)
     const ap_float2 zk[8] = {z[0][0], z[0][1], z[3][1], z[3][0], z[1][0], z[1][1], z[2][1], z[2][0]};
     const ap_float2 zm[8] = {p.l0 ? z[0][0] : z[3][3], p.l0 ? z[0][3] : z[3][2], p.l0 ? z[3][2] : z[0][2],
@@ -238,7 +247,7 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) ap_mel2048_run_kernel(ApMelWa
     const int lane = tid & 63;
     const int wave = AP_UNIFORM(tid >> 6);
     ap_float2 *X = reinterpret_cast<ap_float2 *>(ap_smem) + wave * APW_X_COMPLEX;
-    ap_float2 *TW2 = reinterpret_cast<ap_float2 *>(ap_smem + P.off_tw2);               // [4][18]
+    ap_float2 *TW2 = reinterpret_cast<ap_float2 *>(ap_smem + P.off_tw2);               // [64][14]
     const ap_float2 *TW1 = reinterpret_cast<const ap_float2 *>(ap_smem + P.off_tw1);   // [64][18]
     const ap_float2 *WIN = reinterpret_cast<const ap_float2 *>(ap_smem + P.off_win);   // [1024] pairs
     const ap_float4 *WQ = reinterpret_cast<const ap_float4 *>(ap_smem + P.off_wq);     // [n_quads]
@@ -258,13 +267,14 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) ap_mel2048_run_kernel(ApMelWa
     const ApwLane lc = apw_lane_init(lane, TW2, P.tw, APM_TW_ROW);
     const ApmPairLane pl = apm_pair_lane_init(lane);
     // per-lane tables kept in registers (REGS): straight from the global tables
-    ap_float2 winr[16], t1r[16], t2r[16], wsp[8];
+    ap_float2 winr[16], t1r[16], t2r[12], wsp[8];
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
         winr[j] = (REGS & APM_REG_WIN) ? reinterpret_cast<const ap_float2 *>(P.window)[lane + 64 * j] : ap_mk(0.0f, 0.0f);
         if (IN16 == 1) winr[j] = ap_scale(winr[j], 1.0f / 32768.0f);      // 16-bit PCM -> [-1, 1): folded into the window
-        t1r[j] = (REGS & APM_REG_TW1) ? P.tw[(2 * lane * j) & 2047] : ap_mk(0.0f, 0.0f);        // W_1024^(lane j)
-        t2r[j] = (REGS & APM_REG_TW2) ? P.tw[32 * (lane & 3) * j] : ap_mk(0.0f, 0.0f);
+        t1r[j] = (REGS & APM_REG_TW1) ? P.tw[2 * (4 * j + (lane & 3)) * (lane >> 2)] : ap_mk(0.0f, 0.0f);
+        if (j < 12)
+            t2r[j] = (REGS & APM_REG_TW2) ? P.tw[32 * (j % 3 + 1) * (apm_lane_group(pl.L, j / 3) >> 4)] : ap_mk(0.0f, 0.0f);
     }
     apm_split_twiddles(pl, P.tw, wsp);
     // frame-invariant contraction state: LDS addresses of this lane's entries
@@ -359,6 +369,7 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) ap_mel2048_run_kernel(ApMelWa
             AP_FAIR_SHARE(wave, NW, f);
             const bool clip_ends = t + 1 == Ti;
             const bool more = f + 1 < f_hi;
+            ap_float2 t2[12];                     // the lane's W_64 twiddles: read in apm_forward, used in apm_split
             {
                 ap_float2 xs[16], ws[16];         // renamings: no instructions
 #pragma unroll
@@ -371,7 +382,7 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) ap_mel2048_run_kernel(ApMelWa
                     for (int j = 0; j < 16; ++j) ws[j] = WIN[lane + 64 * j];
                 }
                 AP_SCHED_FENCE();
-                apm_forward<REGS>(xs, ws, X, TW1 + APM_TW_ROW * lane, lc.tw2row, t1r, t2r, lc);
+                apm_forward<REGS>(xs, ws, X, TW1 + APM_TW_ROW * lane, TW2 + APM_TW2_ROW * lane, t1r, t2r, t2, lc);
             }
             // The next frame of this wave's stretch, in flight during split + contraction
             AP_SCHED_FENCE();
@@ -399,7 +410,7 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) ap_mel2048_run_kernel(ApMelWa
                 }
             }
             AP_SCHED_FENCE();
-            apm_split<PMODE>(X, pp, pl, wsp, lc, P.power);
+            apm_split<PMODE>(X, pp, pl, wsp, t2, lc, P.power);
             AP_WAVE_SYNC();
             // ---- plan-based contraction: NPASS branch-free passes (kernels_wave.h) -------------
 #pragma unroll
@@ -546,12 +557,13 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) ap_spec2048_run_kernel(ApSpec
     AP_LDS_BARRIER();
     const ApwLane lc = apw_lane_init(lane, TW2, P.tw, APM_TW_ROW);
     const ApmPairLane pl = apm_pair_lane_init(lane);
-    ap_float2 winr[16], t1r[16], t2r[16], wsp[8];
+    ap_float2 winr[16], t1r[16], t2r[12], wsp[8];
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
         winr[j] = (REGS & APM_REG_WIN) ? reinterpret_cast<const ap_float2 *>(P.window)[lane + 64 * j] : ap_mk(0.0f, 0.0f);
-        t1r[j] = (REGS & APM_REG_TW1) ? P.tw[(2 * lane * j) & 2047] : ap_mk(0.0f, 0.0f);
-        t2r[j] = (REGS & APM_REG_TW2) ? P.tw[32 * (lane & 3) * j] : ap_mk(0.0f, 0.0f);
+        t1r[j] = (REGS & APM_REG_TW1) ? P.tw[2 * (4 * j + (lane & 3)) * (lane >> 2)] : ap_mk(0.0f, 0.0f);
+        if (j < 12)
+            t2r[j] = (REGS & APM_REG_TW2) ? P.tw[32 * (j % 3 + 1) * (apm_lane_group(pl.L, j / 3) >> 4)] : ap_mk(0.0f, 0.0f);
     }
     apm_split_twiddles(pl, P.tw, wsp);
     float fk[17];                                             // bin centres of this lane's bins
@@ -586,6 +598,7 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) ap_spec2048_run_kernel(ApSpec
         constexpr int NROT = (ROT + 1) % U;
         const bool clip_ends = t + 1 == Ti;
         const bool more = f + 1 < f_hi;
+        ap_float2 t2[12];
         {
             ap_float2 xs[16], ws[16];
 #pragma unroll
@@ -598,7 +611,7 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) ap_spec2048_run_kernel(ApSpec
                 for (int j = 0; j < 16; ++j) ws[j] = WIN[lane + 64 * j];
             }
             AP_SCHED_FENCE();
-            apm_forward<REGS>(xs, ws, X, TW1 + APM_TW_ROW * lane, lc.tw2row, t1r, t2r, lc);
+            apm_forward<REGS>(xs, ws, X, TW1 + APM_TW_ROW * lane, TW2 + APM_TW2_ROW * lane, t1r, t2r, t2, lc);
         }
         AP_SCHED_FENCE();
         if (more) {
@@ -614,7 +627,7 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) ap_spec2048_run_kernel(ApSpec
             }
         }
         AP_SCHED_FENCE();
-        apm_split<PMODE>(X, pp, pl, wsp, lc, P.power);
+        apm_split<PMODE>(X, pp, pl, wsp, t2, lc, P.power);
         AP_WAVE_SYNC();
         // ---- this lane's 16 (17) contiguous bins -------------------------------------------
         float v[17];

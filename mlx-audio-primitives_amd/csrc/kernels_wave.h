@@ -171,7 +171,8 @@ struct ApwLane {
     ap_float2 half, halfc;         // (1/2, 1/2), (1/2, -1/2)
 };
 
-// (tw2_stride: complex per row of TW2 - 17 for apw_fill_tables, APM_TW_ROW for apm_fill_tables)
+// (tw2_stride: complex per row of TW2, 17 for apw_fill_tables; the run kernels of kernels_mel2048.h read a
+// row of their own per lane, TW2 + APM_TW2_ROW * lane, and leave tw2row unused)
 AP_DEV ApwLane apw_lane_init(int lane, const ap_float2 *TW2, const ap_float2 *tw, int tw2_stride = 17) {
     ApwLane c;
     c.lane = lane;
@@ -202,20 +203,34 @@ AP_DEV void apw_fill_tables(ap_float2 *tw2, ap_float2 *tw1, ap_float2 *win, cons
     for (int i = tid; i < APW_NC; i += nt) win[i] = reinterpret_cast<const ap_float2 *>(window)[i];
 }
 
-// The same tables for the run kernels (kernels_mel2048.h), in rows of APM_TW_ROW = 18 complex (144 bytes):
-// W_64^(a c) [4][18] and W_1024^(lane k) [64][18], entry k of a row at k < 16, the last two zero.  A lane's
-// 15 twiddles are then eight aligned 16-byte reads (entry 0 = W^0 rides along unused) instead of 15 8-byte
-// reads at half the LDS rate, and the row stride of 36 dwords keeps the reads conflict-free (tools/lds_banks.py).
-// Same values as apw_fill_tables<false>.
+// Lane layout of the run kernels' in-register radix-4 + split (kernels_mel2048.h, ApmPairLane): the lane's
+// index L, the lane permuted within its half (0, 16, 20, 4, 24, 8, 12, 28 for the eight quads), and its
+// four radix-4 groups L, L + 64, 192 - L, 256 - L (L = 0: 0, 64, 192, 128)
+AP_DEV int apm_lane_index(int lane) {
+    return (int)((0xE311825200ull >> (5 * ((lane >> 2) & 7))) & 31) + (lane & 3) + (lane & 32);
+}
+AP_DEV int apm_lane_group(int L, int s) {
+    return s == 0 ? L : s == 1 ? L + 64 : s == 2 ? 192 - L : 256 - (L == 0 ? 128 : L);
+}
+
+// The twiddle tables of the run kernels (kernels_mel2048.h), one row per lane, applied on the READ side of
+// the two exchanges (the values travel untwiddled and the products are folded into the butterflies that
+// consume them, fft_lds.h):
+//   tw1 [64][APM_TW_ROW = 18]: lane l' = 4 k + a reads element i of exchange #1 from lane 4 i + a, which
+//       owes it W_1024^((4 i + a) k): entry i < 16, the last two zero; eight aligned 16-byte reads.
+//   tw2 [64][APM_TW2_ROW = 14]: the lane's four groups g_s out of exchange #2 owe their inputs a = 1..3
+//       W_64^(a c), c = g_s >> 4: entry 3 s + a - 1 < 12, the last two zero; six reads (a = 0 needs none).
+// Row strides of 36 and 28 dwords keep the reads conflict-free (tools/lds_banks.py).
 AP_DEV void apm_fill_tables(ap_float2 *tw2, ap_float2 *tw1, ap_float2 *win, const ap_float2 *tw,
                             const float *window, int tid, int nt) {
-    if (tid < APM_TW2_COMPLEX) {
-        const int a = tid / APM_TW_ROW, c = tid % APM_TW_ROW;
-        tw2[tid] = c < 16 ? tw[32 * a * c] : ap_mk(0.0f, 0.0f);
+    for (int i = tid; i < APM_TW2_COMPLEX; i += nt) {
+        const int l = i / APM_TW2_ROW, e = i % APM_TW2_ROW;
+        const int c = apm_lane_group(apm_lane_index(l), e / 3) >> 4, a = e % 3 + 1;
+        tw2[i] = e < 12 ? tw[32 * a * c] : ap_mk(0.0f, 0.0f);
     }
     for (int i = tid; i < APM_TW1_COMPLEX; i += nt) {
-        const int l = i / APM_TW_ROW, k = i % APM_TW_ROW;
-        tw1[i] = k < 16 ? tw[2 * l * k] : ap_mk(0.0f, 0.0f);
+        const int l = i / APM_TW_ROW, e = i % APM_TW_ROW;
+        tw1[i] = e < 16 ? tw[2 * (4 * e + (l & 3)) * (l >> 2)] : ap_mk(0.0f, 0.0f);
     }
     for (int i = tid; i < APW_NC; i += nt) win[i] = reinterpret_cast<const ap_float2 *>(window)[i];
 }

@@ -55,6 +55,10 @@ if __name__ == "__main__":
     for S in (16, 18, 20):
         r = sum(cycles("r128", (lanes * S + 2 * i) * 8) for i in range(8))
         print(f"tw1 rows S={S}: read {r} bank cycles (ideal 32) for 8 ds_read_b128 = 8 x 1024 bytes")
+    # second table of the run kernels: 12 twiddles per lane (W_64^(a c) of its four radix-4 groups), six reads
+    for S in (12, 14, 16, 18):
+        r = sum(cycles("r128", (lanes * S + 2 * i) * 8) for i in range(6))
+        print(f"tw2 rows S={S}: read {r} bank cycles (ideal 24) for 6 ds_read_b128 = 6 x 1024 bytes")
     # The old [16][64] table: 15 ds_read_b64 of consecutive lanes.  cycles() counts BANK passes only (one per
     # group of lanes without a conflict), not the issue rate of the instruction form: 30 conflict-free passes
     # here move 15 x 512 bytes, 256 bytes per pass, the rows above 32 passes of 256 bytes.  The compiler pairs
