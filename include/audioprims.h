@@ -748,6 +748,43 @@ int ap_dtw_backtrack_i32(const float *D /*dev or NULL*/, const uint8_t *steps /*
                          const int32_t *steps_ab /*host (2 n_steps)*/, int subseq, int32_t *path /*dev*/, int32_t *len /*dev*/,
                          void *stream);
 
+/* piptrack / estimate_tuning / pitch_tuning (pitch.py): the definition of DESIGN.md 9.10 (csrc/kernels_piptrack.h).
+ * S: (B, F, T) magnitudes, rows in_row_stride elements apart (>= T; the padding is never read), clips F rows apart;
+ * in_kind 0: float32, 1: complex64 as (re, im), |z| = sqrtf(fmaf(im, im, re re)) taken on load.  Per frame, with
+ * a, b, c = S[k-1], S[k], S[k+1], every operation rounded on its own:
+ *   avg = 0.5 (c - a);  den = (2 b - c) - a;  shift = avg / (den + (|den| < FLT_MIN ? 1 : 0));  avg = shift = 0 at k = F - 1
+ *   ref_value = threshold max_k S[k] (ref_mode 0), ref_value as given (1), |ref[b, t]| (2; ref (B, T) dense)
+ *   X[k] = S[k] > ref_value ? S[k] : 0;  peak(k) = X[k] > X[k-1] and X[k] >= X[min(k+1, F-1)] and max(k_lo, 1) <= k < k_hi
+ *   pitch = peak ? ((float)k + shift) bin_hz : 0;  magnitude = peak ? S[k] + (0.5 avg) shift : 0
+ * ap_piptrack_f32 writes pitches and magnitudes (B, F, T) float32, rows out_row_stride apart (the padding is never
+ * written).  ap_piptrack_records_f32 writes nothing dense: every peak with pitch > 0 leaves the pair (magnitude, pitch) in
+ * records (G, capacity, 2), G = per_clip ? B : 1, in no particular order, and counters[g] (zeroed by the call) ends as
+ * the number of peaks of group g whether they fitted or not (records beyond capacity are dropped).
+ * AP_ERR_INVALID: NULL buffers, empty sizes, F < 2, strides, k_lo / k_hi outside 0 <= k_lo <= k_hi <= F, a negative
+ * threshold, unknown in_kind / ref_mode; AP_ERR_UNSUPPORTED: capacity above ap_piptrack_max_records().
+ *
+ * ap_piptrack_tuning_f32: per group with n = counters[g] <= capacity records (a group with more is left untouched):
+ * threshold_out[g] = the float32 median of the magnitudes (odd n: the order statistic n / 2; even n: (m[n/2 - 1] +
+ * m[n/2]) 0.5f; n = 0: 0), found exactly by a radix select; counts (G, n_bins): the histogram of the residuals
+ *   r = fmod(bins_per_octave log2((double)pitch / 27.5), 1) taken into [-0.5, 0.5), in float64,
+ * of the records with magnitude >= threshold, over the bins edges[i] <= r < edges[i+1] (edges: device, n_bins + 1
+ * doubles, ascending from -0.5 to 0.5).  ap_pitch_hist_f32: the same histogram of n frequencies, those not > 0 skipped;
+ * counts (n_bins) is zeroed by the call.  n_bins <= ap_piptrack_max_bins(). */
+int ap_piptrack_max_bins(void);
+int ap_piptrack_max_records(void);
+int ap_piptrack_f32(const float *S /*dev*/, int in_kind, int64_t B, int F, int64_t T, int64_t in_row_stride, int k_lo, int k_hi,
+                    float threshold, int ref_mode, float ref_value, const float *ref /*dev (B*T) or NULL*/, float bin_hz,
+                    float *pitches /*dev*/, float *magnitudes /*dev*/, int64_t out_row_stride, void *stream);
+int ap_piptrack_records_f32(const float *S /*dev*/, int in_kind, int64_t B, int F, int64_t T, int64_t in_row_stride, int k_lo,
+                            int k_hi, float threshold, int ref_mode, float ref_value, const float *ref /*dev (B*T) or NULL*/,
+                            float bin_hz, int per_clip, float *records /*dev*/, int64_t capacity, uint64_t *counters /*dev (G)*/,
+                            void *stream);
+int ap_piptrack_tuning_f32(const float *records /*dev*/, const uint64_t *counters /*dev (G)*/, int64_t G, int64_t capacity,
+                           double bins_per_octave, const double *edges /*dev (n_bins+1)*/, int n_bins,
+                           float *threshold_out /*dev (G)*/, uint64_t *counts /*dev (G*n_bins)*/, void *stream);
+int ap_pitch_hist_f32(const float *frequencies /*dev*/, int64_t n, double bins_per_octave, const double *edges /*dev (n_bins+1)*/,
+                      int n_bins, uint64_t *counts /*dev (n_bins)*/, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -67,6 +67,8 @@ ABI_SYMBOLS = [
     "ap_chroma_max_out", "ap_chroma_fold_f32", "ap_chroma_max_smooth", "ap_chroma_cens_f32",
     "ap_dtw_max_features", "ap_dtw_max_steps", "ap_dtw_max_step", "ap_dtw_max_len",
     "ap_dtw_cost_f32", "ap_dtw_accumulate_f32", "ap_dtw_backtrack_i32",
+    "ap_piptrack_max_bins", "ap_piptrack_max_records", "ap_piptrack_f32", "ap_piptrack_records_f32", "ap_piptrack_tuning_f32",
+    "ap_pitch_hist_f32",
     "ap_pcm16_to_f32", "ap_melspec_pcm16_fused", "ap_melspec_pcm16_f32",
 ]
 
@@ -165,6 +167,12 @@ def _declare(lib) -> None:
         "ap_dtw_cost_f32": [P, P, L, I, L, L, L, L, I, P, L, P],
         "ap_dtw_accumulate_f32": [P, L, L, L, L, I, P, P, P, I, I, L, P, L, P, L, P],
         "ap_dtw_backtrack_i32": [P, P, P, L, L, L, L, L, I, P, I, P, P, P],
+        "ap_piptrack_max_bins": [],
+        "ap_piptrack_max_records": [],
+        "ap_piptrack_f32": [P, I, L, I, L, L, I, I, F, I, F, P, F, P, P, L, P],
+        "ap_piptrack_records_f32": [P, I, L, I, L, L, I, I, F, I, F, P, F, I, P, L, P, P],
+        "ap_piptrack_tuning_f32": [P, P, L, L, ctypes.c_double, P, I, P, P, P],
+        "ap_pitch_hist_f32": [P, L, ctypes.c_double, P, I, P, P],
         "ap_pcm16_to_f32": [P, L, F, P, P],
         "ap_melspec_pcm16_fused": [L, I, I, I, I, I, F, P],
         "ap_melspec_pcm16_f32": [P, L, L, I, I, P, P, I, I, L, P, P, P, I, F, P, P, P, P],

@@ -13,7 +13,7 @@ util.normalize with fill=None).  The matrices w are built on the host in float64
 per device under their content.
 
 Deviations from librosa, on purpose.  tuning defaults to 0.0 where librosa's default None estimates it from the signal;
-tuning=None raises ValueError (estimate_tuning is not implemented).  chroma_cqt reads this package's direct-form cqt
+tuning=None raises ValueError (pass tuning=estimate_tuning(y=y, sr=sr, bins_per_octave=...)).  chroma_cqt reads this package's direct-form cqt
 (any hop_length >= 1, nothing decimated); cqt_mode other than "full" raises.  No parity with librosa's numbers is
 claimed: the specification is the float64 definition in tests/chroma_ref.py.
 """
@@ -55,8 +55,8 @@ def _n_chroma_arg(n_chroma):
 
 def _tuning_arg(tuning):
     if tuning is None:
-        raise ValueError("tuning=None (estimate the tuning from the signal) needs estimate_tuning, which is not "
-                         "implemented; pass tuning as a number of bins")
+        raise ValueError("tuning=None (estimate the tuning from the signal) is not done here; pass "
+                         "tuning=estimate_tuning(y=y, sr=sr, bins_per_octave=...) or a number of bins")
     if not _is_real(tuning) or not math.isfinite(float(tuning)):
         raise ValueError(f"tuning must be a finite number, got {tuning!r}")
     return float(tuning)

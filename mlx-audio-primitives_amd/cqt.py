@@ -143,8 +143,8 @@ def _parameters(sr, hop_length, fmin, n_bins, bins_per_octave, tuning, filter_sc
     if intervals != "equal":
         raise ValueError(f"intervals: only 'equal' is implemented, got {intervals!r}")
     if tuning is None:
-        raise ValueError("tuning=None (estimate the tuning from the signal) needs estimate_tuning, which is not "
-                         "implemented; pass tuning as a number of bins")
+        raise ValueError("tuning=None (estimate the tuning from the signal) is not done here; pass "
+                         "tuning=estimate_tuning(y=y, sr=sr, bins_per_octave=...) or a number of bins")
     if dtype is not None and dtype not in (np.complex64, torch.complex64, "complex64"):
         raise ValueError(f"dtype must be None or complex64, got {dtype!r}")
     if not _is_real(sr) or not float(sr) > 0.0 or not math.isfinite(float(sr)):
@@ -225,7 +225,8 @@ def cqt(y, *, sr: float = 22050, hop_length: int = 512, fmin=None, n_bins: int =
     y: (samples,) or (batch, samples), float32 or int16 PCM (converted by pcm16_to_float).  fmin=None: C1 =
     32.70319566257483 Hz.  norm: 1, 2, inf or None.  pad_mode: constant, edge or reflect (reflect needs a clip longer
     than half the longest filter, as stft does for n_fft // 2).  hop_length: any integer >= 1.  Evaluated exactly in
-    direct form: res_type and sparsity are accepted and unused; tuning=None is not implemented.
+    direct form: res_type and sparsity are accepted and unused; for tuning=None pass
+    tuning=estimate_tuning(y=y, sr=sr, bins_per_octave=bins_per_octave).
     Returns complex64 (n_bins, T) or (batch, n_bins, T), T = 1 + samples // hop_length."""
     args, pad_code = _parameters(sr, hop_length, fmin, n_bins, bins_per_octave, tuning, filter_scale, norm, sparsity, window,
                                  scale, pad_mode, dtype, 0.0, "equal")

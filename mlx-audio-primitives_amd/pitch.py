@@ -9,6 +9,10 @@ FFTs in NumPy on the host (pitch.py:88-99).
 yin / yin_cmnd (no counterpart in the reference; librosa's signature): the YIN f0 tracker and its
 cumulative-mean-normalised difference curve on the fused wave-per-frame kernel of csrc/kernels_yin.h
 (frame_length 2048 / 1024) or its direct-sum general kernel.
+
+piptrack / estimate_tuning / pitch_tuning (no counterpart in the reference; librosa's signatures): parabolically
+interpolated STFT peaks on one kernel that reads stft's rows in place, and the tuning they favour from a compact
+record buffer, an exact median by radix select and an integer histogram (csrc/kernels_piptrack.h).
 """
 
 from __future__ import annotations
@@ -223,3 +227,294 @@ def yin_cmnd(y, *, fmin, fmax, sr: float = 22050, frame_length: int = 2048, hop_
         _yin_call("ap_yin_cmnd_f32", y, frame_length, hop,
                   lambda tw: (_x.ptr(y), B, L, frame_length, hop, int(center), lo, hi, tw, _x.ptr(out), st))
     return out[0] if one_d else out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# piptrack / pitch_tuning / estimate_tuning (csrc/kernels_piptrack.h; librosa 0.10's signatures)
+# ---------------------------------------------------------------------------------------------------------------------
+_edges_cache: dict[tuple, torch.Tensor] = {}
+
+
+def _bin_range(sr: float, n_fft: int, fmin: float, fmax: float, F: int):
+    """(k_lo, k_hi): the bins with max(fmin, 0) <= k sr / n_fft < min(fmax, sr / 2), in float64, clipped to [0, F]."""
+    import math
+
+    lo, hi = max(float(fmin), 0.0), min(float(fmax), float(sr) / 2.0)
+    if not lo < hi:
+        raise ValueError(f"fmin ({fmin}) must be less than fmax ({fmax}) after clipping to [0, sr / 2]")
+
+    def first_at_or_above(v):
+        k = int(math.ceil(v * n_fft / float(sr)))
+        while k > 0 and (k - 1) * float(sr) / n_fft >= v:
+            k -= 1
+        while k * float(sr) / n_fft < v:
+            k += 1
+        return min(max(k, 0), F)
+
+    return first_at_or_above(lo), first_at_or_above(hi)
+
+
+def _tuning_bins(resolution, bins_per_octave):
+    """Validated (n_bins, float64 edges) of the residual histogram."""
+    import math
+
+    import numpy as np
+
+    from .cqt import _is_real
+    from .onset import _is_int
+
+    if not _is_real(resolution) or not 0.0 < float(resolution) < 1.0:
+        raise ValueError(f"resolution must lie in (0, 1), got {resolution!r}")
+    if not _is_int(bins_per_octave) or bins_per_octave < 1:
+        raise ValueError(f"bins_per_octave must be a positive integer, got {bins_per_octave!r}")
+    n_bins = int(math.ceil(1.0 / float(resolution)))
+    cap = int(_x.lib().ap_piptrack_max_bins())
+    if n_bins > cap:
+        raise ValueError(f"resolution={resolution!r} needs {n_bins} histogram bins, above the kernel's cap of {cap}")
+    return n_bins, np.linspace(-0.5, 0.5, n_bins + 1)
+
+
+def _device_edges(edges, dev) -> torch.Tensor:
+    key = (len(edges), str(dev))
+    hit = _edges_cache.get(key)
+    if hit is None:
+        hit = torch.from_numpy(edges.copy()).to(dev)
+        if len(_edges_cache) >= 32:
+            _edges_cache.pop(next(iter(_edges_cache)))
+        _edges_cache[key] = hit
+    return hit
+
+
+def _piptrack_args(y, sr, S, n_fft, hop_length, fmin, fmax, threshold, ref):
+    """Everything piptrack checks before the device is touched: (n_fft, hop_length, ref_mode, ref_value, ref array)."""
+    import math
+
+    import numpy as np
+
+    from .chroma import _one_of, _sr_arg
+    from .cqt import _is_real
+    from .onset import _is_int
+
+    _one_of(y, S, "S")
+    sr = _sr_arg(sr)
+    for name, v in (("fmin", fmin), ("fmax", fmax)):
+        if not _is_real(v) or math.isnan(float(v)):
+            raise ValueError(f"{name} must be a number, got {v!r}")
+    if not _is_real(threshold) or not float(threshold) >= 0.0:
+        raise ValueError(f"threshold must be non-negative, got {threshold!r}")
+    ref_mode, ref_value, ref_arr = 0, 0.0, None
+    if ref is not None:
+        if callable(ref):
+            if ref is not np.max:
+                raise TypeError("ref: a callable other than numpy.max is not supported; pass None, a number or an array")
+        elif _is_real(ref):
+            if math.isnan(float(ref)):
+                raise ValueError(f"ref must not be NaN, got {ref!r}")
+            ref_mode, ref_value = 1, abs(float(ref))
+        elif isinstance(ref, (torch.Tensor, np.ndarray, list, tuple)):
+            ref_arr = ref if isinstance(ref, torch.Tensor) else torch.as_tensor(np.asarray(ref, dtype=np.float32))
+            if ref_arr.is_complex() or ref_arr.ndim > 2:
+                raise ValueError(f"ref must be real and broadcastable to (batch, frames), got shape {tuple(ref_arr.shape)}")
+            ref_mode = 2
+        else:
+            raise TypeError(f"ref must be None, numpy.max, a number or an array, got {type(ref).__name__}")
+    if S is None:
+        if not _is_int(n_fft) or n_fft < 2:
+            raise ValueError(f"n_fft must be an integer >= 2, got {n_fft!r}")
+        if hop_length is not None and (not _is_int(hop_length) or hop_length < 1):
+            raise ValueError(f"hop_length must be a positive integer or None, got {hop_length!r}")
+    return sr, ref_mode, ref_value, ref_arr
+
+
+def _piptrack_input(y, sr, S, n_fft, hop_length, fmin, fmax, win_length, window, center, pad_mode):
+    """(x (B, F, T) float32 / complex64 on the device, was it 2D?, n_fft, k_lo, k_hi)."""
+    from .chroma import _spectrum
+    from .cqt import _signal
+
+    if S is not None:
+        shape = tuple(S.shape) if hasattr(S, "shape") else ()
+        if len(shape) not in (2, 3):
+            raise ValueError(f"S must be 2D (bins, frames) or 3D (batch, bins, frames), got {len(shape)}D")
+        if shape[-2] < 2:
+            raise ValueError(f"S must hold at least 2 frequency bins, got {shape[-2]}")
+        n_fft = 2 * (shape[-2] - 1)
+        k_lo, k_hi = _bin_range(sr, n_fft, fmin, fmax, shape[-2])
+        x, squeeze = _spectrum(S, "S", allow_complex=True)
+    else:
+        from .stft import stft
+
+        n_fft = int(n_fft)
+        k_lo, k_hi = _bin_range(sr, n_fft, fmin, fmax, n_fft // 2 + 1)
+        yd, squeeze = _signal(y)
+        x = stft(yd, n_fft=n_fft, hop_length=None if hop_length is None else int(hop_length), win_length=win_length,
+                 window=window, center=center, pad_mode=pad_mode)
+    return x, squeeze, n_fft, k_lo, k_hi
+
+
+def _rows_any(x: torch.Tensor):
+    """(tensor, row stride in elements, in_kind) of a (B, F, T) float32 / complex64 device tensor, kept in place when
+    its rows are dense or padded (onset._rows)."""
+    from .onset import _rows
+
+    xr, rs = _rows(x)
+    return xr, rs, int(x.is_complex())
+
+
+def _ref_on_device(ref_arr, B, T, dev):
+    if ref_arr is None:
+        return None
+    r = ref_arr.to(device=dev, dtype=torch.float32)
+    try:
+        r = torch.broadcast_to(r, (B, T))
+    except RuntimeError:
+        raise ValueError(f"ref of shape {tuple(ref_arr.shape)} is not broadcastable to (batch, frames) = ({B}, {T})") from None
+    return r.contiguous()
+
+
+def piptrack(*, y=None, sr: float = 22050, S=None, n_fft: int = 2048, hop_length=None, fmin: float = 150.0,
+             fmax: float = 4000.0, threshold: float = 0.1, win_length=None, window="hann", center: bool = True,
+             pad_mode: str = "constant", ref=None):
+    """Pitch tracking on thresholded, parabolically interpolated STFT peaks (librosa.piptrack's signature).
+
+    y: (samples,) or (batch, samples), float32 or int16 PCM: stft(y), whose (line-padded) complex rows the peak kernel
+    reads in place.  S: a magnitude spectrogram (F, T) or (batch, F, T) instead, real (taken as the magnitude) or complex
+    (|z| is taken on load); n_fft is then 2 (F - 1).  Exactly one of y and S.  hop_length=None: n_fft // 4.  A bin k with
+    max(fmin, 0) <= k sr / n_fft < min(fmax, sr / 2) is a peak when its thresholded magnitude exceeds the bin below and
+    is not below the bin above; the threshold is `threshold` times the frame's maximum (ref=None or numpy.max), |ref|
+    for a number, or |ref| per frame for an array broadcastable to (batch, frames).  Returns (pitches, magnitudes),
+    float32 (F, T) or (batch, F, T) on the input's device and current stream: the interpolated frequency in Hz and the
+    interpolated magnitude at the peaks, zero elsewhere.  The definition is DESIGN.md 9.10 / tests/piptrack_ref.py."""
+    import numpy as np
+
+    sr, ref_mode, ref_value, ref_arr = _piptrack_args(y, sr, S, n_fft, hop_length, fmin, fmax, threshold, ref)
+    x, squeeze, n_fft, k_lo, k_hi = _piptrack_input(y, sr, S, n_fft, hop_length, fmin, fmax, win_length, window, center, pad_mode)
+    B, F, T = x.shape
+    dev = x.device
+    pitches = torch.empty((B, F, T), dtype=torch.float32, device=dev)
+    mags = torch.empty((B, F, T), dtype=torch.float32, device=dev)
+    if B and T:
+        xr, rs, kind = _rows_any(x)
+        rd = _ref_on_device(ref_arr, B, T, dev)
+        _x.check(_x.dlib(dev).ap_piptrack_f32(_x.ptr(xr), kind, B, F, T, rs, k_lo, k_hi, float(threshold), ref_mode, ref_value,
+                                              None if rd is None else _x.ptr(rd), float(np.float32(sr / n_fft)), _x.ptr(pitches),
+                                              _x.ptr(mags), T, _x.stream_ptr(dev)))
+    return (pitches[0], mags[0]) if squeeze else (pitches, mags)
+
+
+def _pick_tuning(counts, edges) -> float:
+    """edges[argmax(counts)], the first maximum winning."""
+    import numpy as np
+
+    return float(edges[int(np.argmax(counts))])
+
+
+def _warn_no_pitch():
+    import warnings
+
+    warnings.warn("Trying to estimate tuning from empty frequency set.", UserWarning, stacklevel=3)
+
+
+def pitch_tuning(frequencies, *, resolution: float = 0.01, bins_per_octave: int = 12) -> float:
+    """The tuning deviation (in fractions of a bin, in [-0.5, 0.5)) that the frequencies favour (librosa.pitch_tuning):
+    the left edge of the fullest bin of the histogram of r = bins_per_octave log2(f / 27.5) mod 1, taken into
+    [-0.5, 0.5), over ceil(1 / resolution) equal bins; r is computed in float64 from the float32 f > 0, the counts are
+    integers (one kernel; the argmax and the edges stay on the host).  frequencies: any tensor or array, on the host or
+    the device.  No positive frequency gives a UserWarning and 0.0."""
+    import numpy as np
+
+    n_bins, edges = _tuning_bins(resolution, bins_per_octave)
+    f = frequencies if isinstance(frequencies, torch.Tensor) else torch.as_tensor(np.asarray(frequencies, dtype=np.float32))
+    if f.is_complex():
+        raise ValueError("frequencies must be real")
+    if f.numel() == 0:
+        _warn_no_pitch()
+        return 0.0
+    f = _x.to_device_f32(f).reshape(-1)
+    dev = f.device
+    counts = torch.empty(n_bins, dtype=torch.int64, device=dev)
+    _x.check(_x.dlib(dev).ap_pitch_hist_f32(_x.ptr(f), f.numel(), float(bins_per_octave), _x.ptr(_device_edges(edges, dev)), n_bins,
+                                            _x.ptr(counts), _x.stream_ptr(dev)))
+    counts = counts.cpu().numpy()
+    if not counts.any():
+        _warn_no_pitch()
+        return 0.0
+    return _pick_tuning(counts, edges)
+
+
+def _tuning_records(x, k_lo, k_hi, threshold, ref_mode, ref_value, ref_arr, bin_hz, per_clip, n_bins, edges, bins_per_octave,
+                    capacity):
+    """(number of peaks, median magnitude, counts, runs) with the first three per group as host arrays (G,), (G,),
+    (G, n_bins): the compact peak kernel and the selection kernel, run again with the exact capacity when the first
+    guess was too small; runs is 1 or 2."""
+    B, F, T = x.shape
+    dev = x.device
+    G = B if per_clip else 1
+    xr, rs, kind = _rows_any(x)
+    rd = _ref_on_device(ref_arr, B, T, dev)
+    cap_max = int(_x.lib().ap_piptrack_max_records())
+    if capacity is None:
+        capacity = max(1024, -(-(B // G) * F * T // 16))              # peaks are 1 to 2 % of the bins on tonal input
+    capacity = min(int(capacity), cap_max)
+    d, st = _x.dlib(dev), _x.stream_ptr(dev)
+    de = _device_edges(edges, dev)
+    counters = torch.empty(G, dtype=torch.int64, device=dev)
+    thr = torch.empty(G, dtype=torch.float32, device=dev)
+    counts = torch.empty((G, n_bins), dtype=torch.int64, device=dev)
+    for attempt in range(2):
+        records = torch.empty((G, capacity, 2), dtype=torch.float32, device=dev)
+        _x.check(d.ap_piptrack_records_f32(_x.ptr(xr), kind, B, F, T, rs, k_lo, k_hi, float(threshold), ref_mode, ref_value,
+                                           None if rd is None else _x.ptr(rd), bin_hz, int(per_clip), _x.ptr(records), capacity,
+                                           _x.ptr(counters), st))
+        _x.check(d.ap_piptrack_tuning_f32(_x.ptr(records), _x.ptr(counters), G, capacity, float(bins_per_octave), _x.ptr(de), n_bins,
+                                          _x.ptr(thr), _x.ptr(counts), st))
+        n = counters.cpu().numpy()
+        need = int(n.max())
+        if need <= capacity:
+            return n, thr.cpu().numpy(), counts.cpu().numpy(), attempt + 1
+        if need > cap_max:
+            raise ValueError(f"estimate_tuning: {need} peaks in one group, above the kernel's cap of {cap_max}; use per_clip=True "
+                             "or a smaller batch")
+        capacity = need
+    raise RuntimeError("estimate_tuning: the peak count changed between two runs on the same input")
+
+
+def estimate_tuning(*, y=None, sr: float = 22050, S=None, n_fft: int = 2048, resolution: float = 0.01,
+                    bins_per_octave: int = 12, **kwargs):
+    """The tuning deviation of a signal or spectrogram in fractions of a bin (librosa.estimate_tuning's signature):
+    pitch_tuning of the piptrack peaks whose magnitude is at least the median peak magnitude.  y, S, n_fft and
+    **kwargs (hop_length, fmin, fmax, threshold, win_length, window, center, pad_mode, ref) are piptrack's.  Returns one
+    Python float over the whole input, batched or not, as librosa does; per_clip=True with batched input returns a
+    float64 array (batch,), every clip with its own median and histogram.  Nothing dense is written: the peak kernel
+    leaves (magnitude, pitch) records, a second kernel selects the median exactly and counts the residuals (DESIGN.md
+    9.10).  Pass the result on as `tuning=` to cqt / chroma_stft / chroma_cqt (in their bins_per_octave / n_chroma)."""
+    import numpy as np
+
+    per_clip = kwargs.pop("per_clip", False)
+    capacity = kwargs.pop("_capacity", None)
+    allowed = ("hop_length", "fmin", "fmax", "threshold", "win_length", "window", "center", "pad_mode", "ref")
+    unknown = sorted(k for k in kwargs if k not in allowed)
+    if unknown:
+        raise TypeError(f"estimate_tuning got unexpected keyword arguments {unknown}; piptrack's are {list(allowed)}")
+    if not isinstance(per_clip, (bool, np.bool_)):
+        raise ValueError(f"per_clip must be a bool, got {per_clip!r}")
+    if capacity is not None and (not isinstance(capacity, int) or capacity < 1):
+        raise ValueError(f"_capacity must be a positive integer, got {capacity!r}")
+    kw = dict(hop_length=None, fmin=150.0, fmax=4000.0, threshold=0.1, win_length=None, window="hann", center=True,
+              pad_mode="constant", ref=None)
+    kw.update(kwargs)
+    sr, ref_mode, ref_value, ref_arr = _piptrack_args(y, sr, S, n_fft, kw["hop_length"], kw["fmin"], kw["fmax"], kw["threshold"],
+                                                      kw["ref"])
+    n_bins, edges = _tuning_bins(resolution, bins_per_octave)
+    x, squeeze, n_fft, k_lo, k_hi = _piptrack_input(y, sr, S, n_fft, kw["hop_length"], kw["fmin"], kw["fmax"], kw["win_length"],
+                                                    kw["window"], kw["center"], kw["pad_mode"])
+    B, F, T = x.shape
+    per_clip = bool(per_clip) and not squeeze
+    if B == 0 or T == 0:
+        n, counts = np.zeros(B if per_clip else 1, np.int64), np.zeros((B if per_clip else 1, n_bins), np.int64)
+    else:
+        n, _, counts, _ = _tuning_records(x, k_lo, k_hi, kw["threshold"], ref_mode, ref_value, ref_arr,
+                                          float(np.float32(sr / n_fft)), per_clip, n_bins, edges, bins_per_octave, capacity)
+    out = np.array([_pick_tuning(counts[g], edges) if n[g] > 0 else 0.0 for g in range(len(n))], np.float64)
+    if (n == 0).any():
+        _warn_no_pitch()
+    return out if per_clip else float(out[0])
