@@ -748,6 +748,41 @@ int ap_dtw_backtrack_i32(const float *D /*dev or NULL*/, const uint8_t *steps /*
                          const int32_t *steps_ab /*host (2 n_steps)*/, int subseq, int32_t *path /*dev*/, int32_t *len /*dev*/,
                          void *stream);
 
+/* recurrence_matrix / cross_similarity / recurrence_to_lag / lag_to_recurrence (segment.py): k-nearest-neighbour
+ * matrices, the definition of DESIGN.md 9.11 (csrc/kernels_segment.h).  ref (B, d, n_ref) and data (B, d, n) float32, rows
+ * ref_row_stride / data_row_stride apart; D[i, j] = metric(ref[:, i], data[:, j]) with the metrics and the bits of the
+ * DTW cost kernel; D is never stored.  Caps: d as for DTW, n and n_ref <= ap_segment_max_len().  Frame i is eligible
+ * for query j when |i - j| >= width (width > 0 needs n_ref == n) and D[i, j] is no NaN.
+ *
+ * ap_segment_threshold_f32: records (B, n, 2) of 32-bit words: the bits of tau_j, the k-th smallest eligible distance of
+ * query j (k clipped to the eligible frames), and t_j (int32), the largest index admitted among the frames tied at
+ * tau_j; (NaN, -1) when no frame is eligible.  Frame i is a neighbour of j when (D[i, j], i) <= (tau_j, t_j).
+ *
+ * ap_segment_bandwidth_f32: bw (B) float32 from tau_j over the queries with t_j >= 0: kind 0 their median (an even
+ * count: fl(fl(a + b) 0.5f) of the middle two), 1 their mean, 2 their geometric mean (float64 sums in a fixed order,
+ * rounded once); NaN when no query has a neighbour.
+ *
+ * ap_segment_write_f32: out (B, n_ref, n), rows out_row_stride apart, uint8 for mode 0 (connectivity: 1), float32 for
+ * mode 1 (distance: D) and 2 (affinity: 2^(D fl32(-log2(e) / bw)), bw = bw[b] (dev) when given, else `bandwidth`); 0
+ * where i is no neighbour of j.  full: every eligible frame counts as one.  sym (n_ref == n): also j must be a
+ * neighbour of i.  self_diag (n_ref == n), applied last: the diagonal is 1 (modes 0, 2) or 0 (mode 1).  Every cell of
+ * the payload is written once, nothing behind a row's n columns.
+ *
+ * ap_segment_lag: elements of elem_bytes (1 or 4).  to_lag: in (B, n, n), out (B, t_lag, n), t_lag = n or 2 n,
+ * out[(i - j) mod t_lag, j] = in[i, j], 0 in the rows no i maps to; else in (B, t_lag, n), out (B, n, n),
+ * out[i, j] = in[(i - j) mod t_lag, j]. */
+int ap_segment_max_len(void);
+int ap_segment_threshold_f32(const float *ref /*dev*/, const float *data /*dev*/, int64_t B, int d, int64_t n_ref, int64_t n,
+                             int64_t ref_row_stride, int64_t data_row_stride, int metric, int64_t k, int64_t width,
+                             uint32_t *records /*dev*/, void *stream);
+int ap_segment_bandwidth_f32(const uint32_t *records /*dev*/, int64_t B, int64_t n, int kind, float *bw /*dev*/, void *stream);
+int ap_segment_write_f32(const float *ref /*dev*/, const float *data /*dev*/, int64_t B, int d, int64_t n_ref, int64_t n,
+                         int64_t ref_row_stride, int64_t data_row_stride, int metric, int mode, int64_t width, int full, int sym,
+                         int self_diag, const uint32_t *records /*dev*/, const float *bw /*dev (B) or NULL*/, double bandwidth,
+                         void *out /*dev*/, int64_t out_row_stride, void *stream);
+int ap_segment_lag(const void *in /*dev*/, int64_t B, int64_t n, int64_t t_lag, int elem_bytes, int to_lag, int64_t in_row_stride,
+                   void *out /*dev*/, int64_t out_row_stride, void *stream);
+
 /* piptrack / estimate_tuning / pitch_tuning (pitch.py): the definition of DESIGN.md 9.10 (csrc/kernels_piptrack.h).
  * S: (B, F, T) magnitudes, rows in_row_stride elements apart (>= T; the padding is never read), clips F rows apart;
  * in_kind 0: float32, 1: complex64 as (re, im), |z| = sqrtf(fmaf(im, im, re re)) taken on load.  Per frame, with

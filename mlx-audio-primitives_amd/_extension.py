@@ -69,6 +69,7 @@ ABI_SYMBOLS = [
     "ap_dtw_cost_f32", "ap_dtw_accumulate_f32", "ap_dtw_backtrack_i32",
     "ap_piptrack_max_bins", "ap_piptrack_max_records", "ap_piptrack_f32", "ap_piptrack_records_f32", "ap_piptrack_tuning_f32",
     "ap_pitch_hist_f32",
+    "ap_segment_max_len", "ap_segment_threshold_f32", "ap_segment_bandwidth_f32", "ap_segment_write_f32", "ap_segment_lag",
     "ap_pcm16_to_f32", "ap_melspec_pcm16_fused", "ap_melspec_pcm16_f32",
 ]
 
@@ -173,6 +174,11 @@ def _declare(lib) -> None:
         "ap_piptrack_records_f32": [P, I, L, I, L, L, I, I, F, I, F, P, F, I, P, L, P, P],
         "ap_piptrack_tuning_f32": [P, P, L, L, ctypes.c_double, P, I, P, P, P],
         "ap_pitch_hist_f32": [P, L, ctypes.c_double, P, I, P, P],
+        "ap_segment_max_len": [],
+        "ap_segment_threshold_f32": [P, P, L, I, L, L, L, L, I, L, L, P, P],
+        "ap_segment_bandwidth_f32": [P, L, L, I, P, P],
+        "ap_segment_write_f32": [P, P, L, I, L, L, L, L, I, I, L, I, I, I, P, P, ctypes.c_double, P, L, P],
+        "ap_segment_lag": [P, L, L, L, I, I, L, P, L, P],
         "ap_pcm16_to_f32": [P, L, F, P, P],
         "ap_melspec_pcm16_fused": [L, I, I, I, I, I, F, P],
         "ap_melspec_pcm16_f32": [P, L, L, I, I, P, P, I, I, L, P, P, P, I, F, P, P, P, P],
