@@ -259,8 +259,9 @@ static inline int ap_prepare_mel_wave(ApMelWaveParams &W, const ApStftParams &P,
     return AP_OK;
 }
 
-// n_fft = 2048 run kernel (kernels_mel2048.h): 12 waves per CU, output runs in registers.  Returns 1
-// when the shape is not one it serves (the caller then takes ap_mel2048_wave_kernel).
+// n_fft = 2048 run kernel (kernels_mel2048.h): 8 waves per CU, output runs in registers.  Returns 1
+// when the shape is not one it serves (the caller then takes ap_mel2048_wave_kernel).  W.pair tells the
+// launcher which instantiation the LDS carve-up is for (hop 512: pair contraction where the parking planes fit).
 //   n_waves / x_complex / partial_off: APM_WAVES, APW_X_COMPLEX, APM_PARTIAL_OFF of the kernel header
 static inline int ap_prepare_mel_run(ApMelWaveParams &W, const ApStftParams &P, int64_t B, const int32_t *plan,
                                      const int32_t *desc, int n_waves, int x_complex, int partial_off,
@@ -300,11 +301,18 @@ static inline int ap_prepare_mel_run(ApMelWaveParams &W, const ApStftParams &P, 
     const int pass = (W.n_parts + 63) / 64;
     if (pass < 1 || pass > 4 || W.n_quads < 256 * pass) return 1;   // a pass reads 4 weight quads per lane
     *n_pass = pass;
-    int off = n_waves * x_complex * (int)sizeof(ap_float2);
-    // twiddle tables in rows of 18 complex (apm_fill_tables): 16-byte aligned rows for ds_read_b128
+    // twiddle tables in rows of 18 complex (apm_fill_tables): 16-byte aligned rows for ds_read_b128; the
+    // window table only for builds that read it from LDS
+    const int tables = (APM_TW2_COMPLEX + APM_TW1_COMPLEX + (APM_MEL_WIN_LDS ? APW_NC : 0)) * (int)sizeof(ap_float2) +
+                       ap_align16(W.n_quads * 16);
+    // hop 512: two frames per contraction (PAIR = 1) where the parking planes fit the LDS next to the
+    // exchange buffers and the tables, and the 8-byte slots fit the idle part of the exchange buffer
+    W.pair = W.hopj == 4 && partial_off + 2 * (W.n_slots + 4) <= 2 * x_complex &&
+             n_waves * (x_complex + APM_PARK_COMPLEX) * (int)sizeof(ap_float2) + tables <= AP_LDS_MAX;
+    int off = n_waves * (x_complex + (W.pair ? APM_PARK_COMPLEX : 0)) * (int)sizeof(ap_float2);
     W.off_tw2 = off; off += APM_TW2_COMPLEX * (int)sizeof(ap_float2);
     W.off_tw1 = off; off += APM_TW1_COMPLEX * (int)sizeof(ap_float2);
-    W.off_win = off; off += APW_NC * (int)sizeof(ap_float2);
+    W.off_win = off; off += APM_MEL_WIN_LDS ? APW_NC * (int)sizeof(ap_float2) : 0;
     W.off_wq = off; off += ap_align16(W.n_quads * 16);
     W.off_parts = off;
     W.off_partial = 0;
@@ -312,7 +320,7 @@ static inline int ap_prepare_mel_run(ApMelWaveParams &W, const ApStftParams &P, 
     W.otile_stride = 0;
     W.lds_bytes = off;
     if (off > AP_LDS_MAX) return 1;
-    // persistent: one 12-wave workgroup per CU, every wave a contiguous stretch of >= 8 frames
+    // persistent: one workgroup of n_waves (8) waves per CU, every wave a contiguous stretch of >= 8 frames
     const int64_t n_frames = B * P.T;
     int64_t g = (n_frames + (int64_t)n_waves * 8 - 1) / ((int64_t)n_waves * 8);
     if (g > 256) g = 256;

@@ -22,6 +22,16 @@
 #define APM_TW2_ROW 14
 #define APM_TW1_COMPLEX (64 * APM_TW_ROW)   // W_1024^((4 i + a) k) of the reading lane 4 k + a, i = 0..15
 #define APM_TW2_COMPLEX (64 * APM_TW2_ROW)  // W_64^(a c) of the lane's four radix-4 groups, a = 1..3
+// Pair contraction of the mel run kernel (hop 512): the |X|^p plane of the first frame of a pair waits in a
+// parking area right behind the wave's exchange buffer - a constant distance from the plane of the second frame,
+// so the pair path needs no address registers of its own.  1040 floats: the plane's 1025 and the read-ahead of the
+// contraction, whose entries always read the groups g, g + 1 and g + 2, g + 3 of four floats (zero weights past a
+// part's end) and start at group 256 at the latest - floats up to 1039.  Nobody writes floats 1025..1039 in the
+// frame loop: the kernel zeroes them once (0 x garbage would be NaN for garbage that is not finite).
+#define APM_PARK_COMPLEX 520
+// The window pairs of the mel run kernel live in registers for the whole kernel (APM_REG_WIN in
+// kernels_mel2048.h): its launches carry no window table in LDS.
+#define APM_MEL_WIN_LDS 0
 
 struct ApMelWaveParams {
     const float *y;            // (B, L)
@@ -37,7 +47,9 @@ struct ApMelWaveParams {
     int hop, pad, pad_mode, n_mels, n_parts, n_quads, n_slots;   // n_slots: partial sums per frame
     int hopj;                  // hop / 128 when the next frame reuses this one's registers (2, 4, 8), else 0
     int max_row_parts;         // largest number of parts of one row
-    int partial_stride;        // floats between the waves' partial-sum arrays (n_slots + dump slot + 3 read-ahead)
+    int pair;                  // run kernel: 1 = the pair-contraction build (PAIR = 1: a parking plane behind every
+                               // exchange buffer, 8-byte partial-sum slots), 0 = one frame per contraction
+    int partial_stride;       // floats between the waves' partial-sum arrays (n_slots + dump slot + 3 read-ahead)
     float power;
     // LDS carve-up (bytes from the start of dynamic LDS)
     int off_tw2, off_tw1, off_win, off_wq, off_parts, off_partial, off_otile, lds_bytes;

@@ -55,18 +55,26 @@ static int ap_launch_mel_wave(const ApMelWaveParams &W, int grid, void *stream) 
 // n_fft = 2048 run kernel (kernels_mel2048.h)
 template <int PMODE, int HOPJ, int IN16>
 static int ap_launch_mel_run_h(const ApMelWaveParams &W, int n_pass, int grid, void *stream) {
+    // hop 512 contracts two frames at a time (PAIR = 1) wherever ap_prepare_mel_run found room for the parking planes:
+    // always, for plans of ap_mel_plan_host (the PAIR = 0 twin is for caller-made plans with larger tables)
+#define AP_RUN_LAUNCH_P(NP, PAIR)                                                                        \
+    do {                                                                                                 \
+        int rc = ap_allow_lds(ap_mel2048_run_kernel<PMODE, NP, HOPJ, IN16, APM_WAVES, APM_REGS, PAIR>, W.lds_bytes); \
+        if (rc != AP_OK) return rc;                                                                      \
+        hipLaunchKernelGGL((ap_mel2048_run_kernel<PMODE, NP, HOPJ, IN16, APM_WAVES, APM_REGS, PAIR>), dim3(grid), \
+                           dim3(64 * APM_WAVES), W.lds_bytes, (hipStream_t)stream, W);                   \
+    } while (0)
 #define AP_RUN_LAUNCH(NP)                                                                                \
     do {                                                                                                 \
-        int rc = ap_allow_lds(ap_mel2048_run_kernel<PMODE, NP, HOPJ, IN16>, W.lds_bytes);                \
-        if (rc != AP_OK) return rc;                                                                      \
-        hipLaunchKernelGGL((ap_mel2048_run_kernel<PMODE, NP, HOPJ, IN16>), dim3(grid), dim3(64 * APM_WAVES), \
-                           W.lds_bytes, (hipStream_t)stream, W);                                         \
+        if (HOPJ == 4 && W.pair) AP_RUN_LAUNCH_P(NP, (HOPJ == 4));                                       \
+        else AP_RUN_LAUNCH_P(NP, 0);                                                                     \
     } while (0)
     if (n_pass == 1) AP_RUN_LAUNCH(1);
     else if (n_pass == 2) AP_RUN_LAUNCH(2);
     else if (n_pass == 3) AP_RUN_LAUNCH(3);
     else AP_RUN_LAUNCH(4);
 #undef AP_RUN_LAUNCH
+#undef AP_RUN_LAUNCH_P
     return ap_check_launch("ap_melspec_f32(run)");
 }
 template <int PMODE, int IN16 = 0>

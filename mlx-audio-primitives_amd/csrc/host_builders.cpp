@@ -227,7 +227,25 @@ const int kB128Groups[4][16] = {
     {32, 33, 34, 35, 44, 45, 46, 47, 52, 53, 54, 55, 56, 57, 58, 59},
     {36, 37, 38, 39, 40, 41, 42, 43, 48, 49, 50, 51, 60, 61, 62, 63}};
 
-void mel_wave_layout(const std::vector<MelPart> &parts, MelWaveLayout &L) {
+// entries of the wave layout: a part of 3-4 groups each, the shorter parts two by two
+int mel_wave_entries(const std::vector<MelPart> &parts) {
+    int whole = 0;
+    for (auto &p : parts) whole += p.ng > 2;
+    return whole + ((int)parts.size() - whole + 1) / 2;
+}
+
+// words of the plan blob (ap_mel_plan_host); the wave layout takes 64 entries and 256 weight quads a pass
+int64_t mel_plan_words_of(int n_mels, const std::vector<MelPart> &parts) {
+    int64_t quads = 0;
+    for (auto &p : parts) quads += p.ng;
+    const int64_t passes = (mel_wave_entries(parts) + 63) / 64;
+    return 2 * (int64_t)n_mels + 4 * (int64_t)parts.size() + 4 * quads + (int64_t)n_mels + 1 + 8 +
+           4 * 64 * passes + 4 * 256 * passes + 8;
+}
+
+// n2048: a bank of 1025 bins.  Only the layouts that ap_mel2048_run_kernel can take (n_fft = 2048 and at most 4
+// passes, ap_prepare_mel_run) get the exchange of entries below; every other plan keeps the dealing alone.
+void mel_wave_layout(const std::vector<MelPart> &parts, bool n2048, MelWaveLayout &L) {
     // parts are sorted by length (longest first): whole entries first, then the pairs
     std::vector<std::pair<int, int>> ent;
     size_t i = 0;
@@ -269,6 +287,72 @@ void mel_wave_layout(const std::vector<MelPart> &parts, MelWaveLayout &L) {
                 L.partB[slot] = ent[grp[g][j]].second;
             }
     }
+    // The dealing above looks at the first group of half A only and never moves an entry to another pass; a pass
+    // whose entries crowd a few residues modulo 16 (the headline bank: one residue 8 times in a pass) cannot be
+    // served without conflicts by any dealing of its own entries.  So: exchange entries between any two positions of
+    // the whole layout while that lowers the bank cycles of the plane reads.  An entry reads the 16-byte groups gA,
+    // gA + 1 (half A) and gB, gB + 1 (half B) with one ds_read_b128 each; the 16 lanes of a lane group take one
+    // LDS cycle when their groups differ modulo 16 (equal groups are one address: a broadcast), N cycles when N
+    // different groups share a residue.  Cost of a (pass, lane group): the largest such N of half A plus that of half
+    // B, then - to get off the plateaus of a maximum - the sum of the squared multiplicities.  Which lane and which
+    // pass computes an entry changes no sum: every entry runs the same FMA chains wherever it sits.
+    // (tools/lds_banks.py --mel-plan, headline plan: 94 -> 50 bank cycles for the 12 reads, ideal 48.)
+    // The search tries every pair of positions, up to 16 times over: quadratic, so it is kept to the run kernel's
+    // plans, at most 256 positions (the headline's 192: about 30 ms, once per bank - the plan is cached).  A wider
+    // plan never reaches that kernel, and the wave kernels of the other n_fft were not measured with it.
+    if (n2048 && passes <= 4) {
+        const int n_pos = passes * 64;
+        auto groups_of = [&](int pos, int &gA, int &gB) {
+            gA = gB = 0;                                       // idle position: group 0 twice
+            if (L.partA[pos] < 0) return;
+            gA = parts[L.partA[pos]].g0;
+            gB = L.partB[pos] >= 0 ? parts[L.partB[pos]].g0 : gA + 2;
+        };
+        auto cost_of = [&](int ps, int g, int &worst, int &squares) {
+            worst = 0; squares = 0;
+            for (int half = 0; half < 2; ++half) {
+                int seen[16][16], n_seen[16] = {};
+                for (int j = 0; j < 16; ++j) {
+                    int gA, gB;
+                    groups_of(ps * 64 + kB128Groups[g][j], gA, gB);
+                    const int grp = half ? gB : gA, r = grp & 15;
+                    bool dup = false;
+                    for (int k = 0; k < n_seen[r]; ++k) dup = dup || seen[r][k] == grp;
+                    if (!dup) seen[r][n_seen[r]++] = grp;
+                }
+                int m = 0;
+                for (int r = 0; r < 16; ++r) { if (n_seen[r] > m) m = n_seen[r]; squares += n_seen[r] * n_seen[r]; }
+                worst += m;
+            }
+        };
+        int lane_group[64];
+        for (int g = 0; g < 4; ++g)
+            for (int j = 0; j < 16; ++j) lane_group[kB128Groups[g][j]] = g;
+        std::vector<int> cw((size_t)passes * 4), cs((size_t)passes * 4);
+        for (int ps = 0; ps < passes; ++ps)
+            for (int g = 0; g < 4; ++g) cost_of(ps, g, cw[ps * 4 + g], cs[ps * 4 + g]);
+        for (int sweep = 0, improved = 1; improved && sweep < 16; ++sweep) {
+            improved = 0;
+            for (int i = 0; i < n_pos; ++i)
+                for (int j = i + 1; j < n_pos; ++j) {
+                    const int ki = (i / 64) * 4 + lane_group[i % 64], kj = (j / 64) * 4 + lane_group[j % 64];
+                    if (ki == kj) continue;
+                    std::swap(L.partA[i], L.partA[j]);
+                    std::swap(L.partB[i], L.partB[j]);
+                    int wi, si, wj, sj;
+                    cost_of(ki / 4, ki % 4, wi, si);
+                    cost_of(kj / 4, kj % 4, wj, sj);
+                    const int dw = wi + wj - cw[ki] - cw[kj], dsq = si + sj - cs[ki] - cs[kj];
+                    if (dw < 0 || (dw == 0 && dsq < 0)) {
+                        cw[ki] = wi; cs[ki] = si; cw[kj] = wj; cs[kj] = sj;
+                        improved = 1;
+                    } else {
+                        std::swap(L.partA[i], L.partA[j]);
+                        std::swap(L.partB[i], L.partB[j]);
+                    }
+                }
+        }
+    }
     // every pass owns four 64-quad weight rows; entry e = 64 p + l reads row i at 256 p + 64 i + l
     L.n_quads = passes * 256;
 }
@@ -279,12 +363,7 @@ int64_t ap_mel_plan_words(const float *fb, int n_mels, int n_bins) {
     std::vector<int> lo, len;
     std::vector<MelPart> parts;
     mel_analyse(fb, n_mels, n_bins, lo, len, parts);
-    int64_t quads = 0;
-    for (auto &p : parts) quads += p.ng;
-    MelWaveLayout L;
-    mel_wave_layout(parts, L);
-    return 2 * (int64_t)n_mels + 4 * (int64_t)parts.size() + 4 * quads + (int64_t)n_mels + 1 + 8 +
-           4 * (int64_t)L.partA.size() + 4 * (int64_t)L.n_quads + 8;
+    return mel_plan_words_of(n_mels, parts);
 }
 
 int ap_mel_plan_host(const float *fb, int n_mels, int n_bins, int32_t *plan, int32_t *desc) {
@@ -298,7 +377,7 @@ int ap_mel_plan_host(const float *fb, int n_mels, int n_bins, int32_t *plan, int
     mel_analyse(fb, M, F, lo, len, parts);
     int64_t quads = 0;
     for (auto &p : parts) quads += p.ng;
-    const int64_t words = ap_mel_plan_words(fb, M, F);
+    const int64_t words = mel_plan_words_of(M, parts);
     std::memset(plan, 0, sizeof(int32_t) * (size_t)words);
     std::memset(desc, 0, sizeof(int32_t) * AP_PLAN_DESC_INTS);
     int64_t off = 0;
@@ -310,7 +389,7 @@ int ap_mel_plan_host(const float *fb, int n_mels, int n_bins, int32_t *plan, int
     const int64_t off_rs = off; off += (int64_t)M + 1;
     off += off & 3 ? 4 - (off & 3) : 0;
     MelWaveLayout WL;
-    mel_wave_layout(parts, WL);
+    mel_wave_layout(parts, F == 1025, WL);
     const int64_t off_wparts = off; off += 4 * (int64_t)WL.partA.size();
     const int64_t off_wquads = off; off += 4 * (int64_t)WL.n_quads;
     for (int m = 0; m < M; ++m) { plan[off_lo + m] = lo[m]; plan[off_len + m] = len[m]; }

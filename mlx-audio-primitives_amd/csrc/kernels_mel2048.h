@@ -30,7 +30,11 @@
 //     "twiddles folded into the butterfly"): 30 packed instructions fewer per frame;
 //   * the 8-frame output run of a lane's two mel rows lives in registers (32 contiguous bytes per
 //     row and lane, as in ap_mel1024_wave_kernel): no output tile in LDS; the partial sums
-//     alias the idle upper half of the wave's exchange buffer.
+//     alias the idle upper half of the wave's exchange buffer;
+//   * with hop 512 the filterbank is contracted for two frames at a time (PAIR, below at the kernel): the
+//     weight quads, the same for every frame, are read once per pair, and the two partial sums of a slot
+//     travel as 8 bytes - 10.6 LDS instructions and 23 LDS-array cycles fewer per frame (profiles/README.md
+//     "Round 7"); the window table is gone from LDS, the window pairs live in registers.
 //
 // Serves constant padding / center=False, power 2 or 1, n_mels <= 128, plans of <= 256 entries
 // whose rows have <= 4 parts; everything else stays on ap_mel2048_wave_kernel.
@@ -172,7 +176,9 @@ AP_DEV void apm_split_twiddles(const ApmPairLane &p, const ap_float2 *tw, ap_flo
     for (int i = 0; i < 8; ++i) wsp[i] = ap_scale(tw[k[i]], 0.5f);
 }
 
-template <int PMODE>
+// POFF: constant float offset of the plane from pp (the mel kernel's parking plane: the stores then share
+// the address registers of the plane in the exchange buffer, the distance is an instruction offset)
+template <int PMODE, int POFF = 0>
 AP_DEV void apm_split(const ap_float2 *X, float *pp, const ApmPairLane &p, const ap_float2 (&wsp)[8],
                       const ap_float2 (&t2)[12], const ApwLane &c, float power) {
     ap_float2 z[4][4];                    // z[s][q] = Z[g_s + 256 q] after the radix-4s
@@ -200,10 +206,10 @@ AP_DEV void apm_split(const ap_float2 *X, float *pp, const ApmPairLane &p, const
         const ap_float2 u = ap_mul_fw(d, wsp[i]);
         const ap_float2 xk = ap_fma_add_mi(a, c.half, u);
         const ap_float2 xm = ap_fma_sub_mi(a, c.half, u);
-        pp[k[i]] = apw_pow2x<PMODE>(xk.x, xk.y, power);
-        pp[APW_NC - k[i]] = apw_pow2x<PMODE>(xm.x, xm.y, power);
+        pp[k[i] + POFF] = apw_pow2x<PMODE>(xk.x, xk.y, power);
+        pp[APW_NC - k[i] + POFF] = apw_pow2x<PMODE>(xm.x, xm.y, power);
     }
-    if (p.l0) pp[APW_NC / 2] = apw_pow2x<PMODE>(z[0][2].x, z[0][2].y, power);   // X[512] = conj Z[512]
+    if (p.l0) pp[APW_NC / 2 + POFF] = apw_pow2x<PMODE>(z[0][2].x, z[0][2].y, power);   // X[512] = conj Z[512]
 }
 
 #ifdef AP_DIAG_STAMPS
@@ -240,13 +246,49 @@ AP_DEV void apm_split(const ap_float2 *X, float *pp, const ApmPairLane &p, const
     } while (0)
 #endif
 
-template <int PMODE, int NPASS, int HOPJ, int IN16 = 0, int NW = APM_WAVES, int REGS = APM_REGS>
+// 16 bytes of a plane or of the weight table as ONE vector load (read through the ap_float4 struct the pair
+// contraction's quads came out as ds_read2_b32 halves)
+#ifdef AP_PACKED_COMPLEX
+AP_DEV ap_float4 apm_load4(const ap_float4 *p) {
+    const apm_float4v v = *reinterpret_cast<const apm_float4v *>(p);
+    ap_float4 r;
+    r.x = v.x; r.y = v.y; r.z = v.z; r.w = v.w;
+    return r;
+}
+#else
+AP_DEV ap_float4 apm_load4(const ap_float4 *p) { return *p; }
+#endif
+
+// PAIR (hop 512 only; the launcher picks it wherever ap_prepare_mel_run found room, P.pair): the filterbank is
+// contracted for two frames at a time.  The four frame bodies of a loop trip are two pairs (rotations 0-1 and
+// 2-3): the frames of the even rotations leave their |X|^p plane in the wave's parking area (APM_PARK_COMPLEX,
+// right behind the exchange buffer), those of the odd rotations in the exchange buffer as ever, and one
+// contraction reads every weight quad once for both planes, runs the FMA chains of each frame in the order of
+// the single-frame contraction, and moves the two partial sums of a slot as one 8-byte store and one 8-byte
+// load.  A pair needs its second frame in the same clip and stretch; a stretch that enters at an odd rotation,
+// a clip end or a stretch end on the first frame of a pair take the single-frame contraction (of the parked
+// plane, for an even rotation) - every frame gets the same bits on either path.  With PAIR the partial-sum
+// slots are 8 bytes apart on both paths (one set of slot addresses).  The launcher (audioprims.hip) is the one
+// place that picks PAIR, from P.pair; the default is what the CPU emulator's launcher instantiates, and the emulator
+// build stops a launch whose carve-up is for the other value.  Every plan of ap_mel_plan_host (<= 4 passes of 256
+// weight quads, <= 512 slots) leaves room for the parking planes: the PAIR = 0 twin of a hop-512 instantiation
+// serves caller-made plans only.
+template <int PMODE, int NPASS, int HOPJ, int IN16 = 0, int NW = APM_WAVES, int REGS = APM_REGS, int PAIR = (HOPJ == 4)>
 __global__ void __launch_bounds__(64 * NW, NW / 4) ap_mel2048_run_kernel(ApMelWaveParams P) {
     static_assert(IN16 != 1 || (REGS & APM_REG_WIN), "the PCM scale rides on the register-resident window");
+    static_assert(APM_MEL_WIN_LDS || (REGS & APM_REG_WIN), "ap_prepare_mel_run leaves no room for a window table");
+    static_assert(!PAIR || HOPJ == 4, "pairs are two of the four rotations of the hop-512 loop");
+    constexpr int XS = APW_X_COMPLEX + (PAIR ? APM_PARK_COMPLEX : 0);     // complex slots between the waves' buffers
+    constexpr int SS = PAIR ? 2 : 1;                                      // floats between two partial-sum slots
+    static_assert(2 * APM_PARK_COMPLEX >= 4 * (APW_NC / 4 + 4), "groups 256 .. 259: the contraction's read-ahead");
+#ifdef AP_HOST_EMU
+    // the emulator's launcher instantiates the default PAIR: the LDS carve-up must be the one for it
+    if ((PAIR != 0) != (P.pair != 0)) { fprintf(stderr, "ap_mel2048_run_kernel: PAIR = %d on a carve-up for pair = %d\n", PAIR, P.pair); abort(); }
+#endif
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = AP_UNIFORM(tid >> 6);
-    ap_float2 *X = reinterpret_cast<ap_float2 *>(ap_smem) + wave * APW_X_COMPLEX;
+    ap_float2 *X = reinterpret_cast<ap_float2 *>(ap_smem) + wave * XS;
     ap_float2 *TW2 = reinterpret_cast<ap_float2 *>(ap_smem + P.off_tw2);               // [64][14]
     const ap_float2 *TW1 = reinterpret_cast<const ap_float2 *>(ap_smem + P.off_tw1);   // [64][18]
     const ap_float2 *WIN = reinterpret_cast<const ap_float2 *>(ap_smem + P.off_win);   // [1024] pairs
@@ -261,7 +303,8 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) ap_mel2048_run_kernel(ApMelWa
         ap_float4 *wq = reinterpret_cast<ap_float4 *>(ap_smem + P.off_wq);
         for (int i = tid; i < P.n_quads; i += nt) wq[i] = reinterpret_cast<const ap_float4 *>(P.quads)[i];
         apm_fill_tables(TW2, reinterpret_cast<ap_float2 *>(ap_smem + P.off_tw1),
-                        reinterpret_cast<ap_float2 *>(ap_smem + P.off_win), P.tw, P.window, tid, nt);
+                        (REGS & APM_REG_WIN) ? nullptr : reinterpret_cast<ap_float2 *>(ap_smem + P.off_win),
+                        P.tw, P.window, tid, nt);
     }
     AP_LDS_BARRIER();
     const ApwLane lc = apw_lane_init(lane, TW2, P.tw, APM_TW_ROW);
@@ -289,9 +332,15 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) ap_mel2048_run_kernel(ApMelWa
         if (pi < P.n_parts) pd = reinterpret_cast<const ap_int4 *>(P.parts)[pi];
         pqa[ps] = reinterpret_cast<const ap_float4 *>(pp) + pd.y;
         pqb[ps] = reinterpret_cast<const ap_float4 *>(pp) + pd.w;
-        sa[ps] = partial + pd.x;
-        sb[ps] = partial + (pd.z < 0 ? P.n_slots : pd.z);
+        sa[ps] = partial + SS * pd.x;
+        sb[ps] = partial + SS * (pd.z < 0 ? P.n_slots : pd.z);
         fz[ps] = pd.z < 0 ? 1.0f : 0.0f;                                  // one long part: both halves to slot A
+    }
+    // PAIR: the read-ahead of the parked plane (floats 1025 .. 2 APM_PARK_COMPLEX - 1) is never written in the
+    // frame loop and is multiplied by zero weights: zero, once (in the exchange buffer these floats are the
+    // wave's own exchange data, finite whenever its samples are)
+    if (PAIR) {
+        for (int i = APW_NC + 1 + lane; i < 2 * APM_PARK_COMPLEX; i += 64) pp[2 * APW_X_COMPLEX + i] = 0.0f;
     }
     int rs0[2], cnt[2];
 #pragma unroll
@@ -299,6 +348,7 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) ap_mel2048_run_kernel(ApMelWa
         const int row = lane + 64 * i;
         rs0[i] = row < M ? P.rowstart[row] : 0;
         cnt[i] = row < M ? P.rowstart[row + 1] - rs0[i] : 0;
+        rs0[i] *= SS;
     }
     AP_LDS_BARRIER();
 
@@ -319,7 +369,7 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) ap_mel2048_run_kernel(ApMelWa
         // end take the index-remapping loader, every other frame the bounds-checked loads
         ApClip clip = ap_clip_make(P.y + (IN16 == 1 ? 0 : b * P.L), IN16 == 1 ? 0 : P.L);
         ApClip16 clip16 = ap_clip16_make(y16 + (IN16 == 1 ? b * P.L : 0), IN16 == 1 ? P.L : 0);
-        auto ld2 = [&](int64_t bb, int base, int p) -> ap_float2 {
+        auto ld2 = [&](int64_t bb, int base, int p) __attribute__((always_inline)) -> ap_float2 {
             if (IN16 == 1) return ap_clip16_load2(clip16, p);
             if (IN16 == 2 && !(base >= 0 && (int64_t)base + 2 * APW_NC <= P.L)) {
                 const float *yb = P.y + bb * P.L;
@@ -362,14 +412,12 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) ap_mel2048_run_kernel(ApMelWa
         int nrun = 0, half = U == 4 ? ((t >> 2) & 1) : 0;
         int64_t f = f_lo;
 
-        // one frame; returns false after the last frame of the stretch
-        auto frame = [&](auto rot_tag) -> bool {
+        // transform of the frame in hand, the loads of the next one and the |X|^p plane, poff_tag floats behind pp
+        auto transform = [&](auto rot_tag, auto poff_tag, const bool clip_ends, const bool more) __attribute__((always_inline)) {
             constexpr int ROT = decltype(rot_tag)::value;
             constexpr int NROT = (ROT + 1) % U;
             AP_FAIR_SHARE(wave, NW, f);
-            const bool clip_ends = t + 1 == Ti;
-            const bool more = f + 1 < f_hi;
-            ap_float2 t2[12];                     // the lane's W_64 twiddles: read in apm_forward, used in apm_split
+            ap_float2 t2[12];                  // the lane's W_64 twiddles: read in apm_forward, used in apm_split
             {
                 ap_float2 xs[16], ws[16];         // renamings: no instructions
 #pragma unroll
@@ -410,41 +458,12 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) ap_mel2048_run_kernel(ApMelWa
                 }
             }
             AP_SCHED_FENCE();
-            apm_split<PMODE>(X, pp, pl, wsp, t2, lc, P.power);
+            apm_split<PMODE, decltype(poff_tag)::value>(X, pp, pl, wsp, t2, lc, P.power);
             AP_WAVE_SYNC();
-            // ---- plan-based contraction: NPASS branch-free passes (kernels_wave.h) -------------
-#pragma unroll
-            for (int ps = 0; ps < NPASS; ++ps) {
-                const ap_float4 *wq = WQ + 256 * ps + lane;
-                ap_float4 w[4], q[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) w[i] = wq[64 * i];
-                q[0] = pqa[ps][0]; q[1] = pqa[ps][1]; q[2] = pqb[ps][0]; q[3] = pqb[ps][1];
-                float acc[2] = {0.0f, 0.0f};
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    acc[i >> 1] = fmaf(w[i].x, q[i].x, acc[i >> 1]);
-                    acc[i >> 1] = fmaf(w[i].y, q[i].y, acc[i >> 1]);
-                    acc[i >> 1] = fmaf(w[i].z, q[i].z, acc[i >> 1]);
-                    acc[i >> 1] = fmaf(w[i].w, q[i].w, acc[i >> 1]);
-                }
-                *sa[ps] = fmaf(fz[ps], acc[1], acc[0]);
-                *sb[ps] = acc[1];
-            }
-            AP_WAVE_SYNC();
-            // ---- row sums (<= 4 adjacent slots per row) into the run's registers ---------------
-            float sum2[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const float p0 = partial[rs0[i]], p1 = partial[rs0[i] + 1], p2 = partial[rs0[i] + 2],
-                            p3 = partial[rs0[i] + 3];
-                float sum = cnt[i] > 0 ? p0 : 0.0f;
-                sum += cnt[i] > 1 ? p1 : 0.0f;
-                sum += cnt[i] > 2 ? p2 : 0.0f;
-                sum += cnt[i] > 3 ? p3 : 0.0f;
-                sum2[i] = sum;
-                vmax = fmaxf(vmax, cnt[i] > 0 ? sum : vmax);
-            }
+        };
+        // the frame's row sums into the run registers, the run's store when it is due, and on to the next frame
+        auto finish = [&](auto rot_tag, const float (&sum2)[2], const bool clip_ends, const bool more) __attribute__((always_inline)) {
+            constexpr int ROT = decltype(rot_tag)::value;
             // the frame's position in the run registers, and the position of the run's first frame
             int pos;
             if (U == 1) {
@@ -488,6 +507,120 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) ap_mel2048_run_kernel(ApMelWa
             }
             if (clip_ends) { t = 0; ++b; } else { ++t; }
             ++f;
+        };
+        constexpr int PARKQ = 2 * APW_X_COMPLEX / 4;              // 16-byte groups from a plane to its parking twin
+        static_assert(2 * APW_X_COMPLEX % 4 == 0 && (APW_X_COMPLEX + APM_PARK_COMPLEX) % 2 == 0, "16-byte aligned planes");
+        // ---- plan-based contraction of one frame: NPASS branch-free passes (kernels_wave.h), then the row sums
+        // (<= 4 adjacent slots per row).  PQ: 0 = the plane in the exchange buffer, PARKQ = the parked one
+        auto contract = [&](auto pq_tag, float (&sum2)[2]) __attribute__((always_inline)) {
+            constexpr int PQ = decltype(pq_tag)::value;
+#pragma unroll
+            for (int ps = 0; ps < NPASS; ++ps) {
+                const ap_float4 *wq = WQ + 256 * ps + lane;
+                ap_float4 w[4], q[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) w[i] = wq[64 * i];
+                q[0] = pqa[ps][PQ]; q[1] = pqa[ps][PQ + 1]; q[2] = pqb[ps][PQ]; q[3] = pqb[ps][PQ + 1];
+                float acc[2] = {0.0f, 0.0f};
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    acc[i >> 1] = fmaf(w[i].x, q[i].x, acc[i >> 1]);
+                    acc[i >> 1] = fmaf(w[i].y, q[i].y, acc[i >> 1]);
+                    acc[i >> 1] = fmaf(w[i].z, q[i].z, acc[i >> 1]);
+                    acc[i >> 1] = fmaf(w[i].w, q[i].w, acc[i >> 1]);
+                }
+                *sa[ps] = fmaf(fz[ps], acc[1], acc[0]);
+                *sb[ps] = acc[1];
+            }
+            AP_WAVE_SYNC();
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const float p0 = partial[rs0[i]], p1 = partial[rs0[i] + SS], p2 = partial[rs0[i] + 2 * SS],
+                            p3 = partial[rs0[i] + 3 * SS];
+                float sum = cnt[i] > 0 ? p0 : 0.0f;
+                sum += cnt[i] > 1 ? p1 : 0.0f;
+                sum += cnt[i] > 2 ? p2 : 0.0f;
+                sum += cnt[i] > 3 ? p3 : 0.0f;
+                sum2[i] = sum;
+                vmax = fmaxf(vmax, cnt[i] > 0 ? sum : vmax);
+            }
+        };
+        // ---- the same for the two frames of a pair (parked plane -> sum0, exchange buffer -> sum1): every weight
+        // quad is read once, each frame's FMA chains run in the order of `contract`, slot s holds (first, second)
+        auto contract_pair = [&](float (&sum0)[2], float (&sum1)[2]) __attribute__((always_inline)) {
+#pragma unroll
+            for (int ps = 0; ps < NPASS; ++ps) {
+                const ap_float4 *wq = WQ + 256 * ps + lane;
+                ap_float4 w[4], q0[4], q1[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) w[i] = apm_load4(wq + 64 * i);
+                q0[0] = apm_load4(pqa[ps] + PARKQ); q0[1] = apm_load4(pqa[ps] + PARKQ + 1);
+                q0[2] = apm_load4(pqb[ps] + PARKQ); q0[3] = apm_load4(pqb[ps] + PARKQ + 1);
+                q1[0] = apm_load4(pqa[ps]); q1[1] = apm_load4(pqa[ps] + 1);
+                q1[2] = apm_load4(pqb[ps]); q1[3] = apm_load4(pqb[ps] + 1);
+                // (AP_PIN on the second frame's accumulators: left alone, the SLP vectoriser pairs the two frames'
+                // chains into v_pk_fma_f32 whose operands - one value of each plane, out of different ds_read_b128 -
+                // first have to be moved next to each other: 88 v_mov_b32 and 48 packed FMAs for 96 plain ones)
+                // (the same holds for the two fz products, which as a packed FMA keep a second copy of fz[ps] in
+                // registers for the whole kernel: the first frame's result is pinned before the second frame's chain ends)
+                float a0[2] = {0.0f, 0.0f}, a1[2] = {0.0f, 0.0f};
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    a0[i >> 1] = fmaf(w[i].x, q0[i].x, a0[i >> 1]);
+                    a0[i >> 1] = fmaf(w[i].y, q0[i].y, a0[i >> 1]);
+                    a0[i >> 1] = fmaf(w[i].z, q0[i].z, a0[i >> 1]);
+                    a0[i >> 1] = fmaf(w[i].w, q0[i].w, a0[i >> 1]);
+                    a1[i >> 1] = fmaf(w[i].x, q1[i].x, a1[i >> 1]); AP_PIN(a1[i >> 1]);
+                    a1[i >> 1] = fmaf(w[i].y, q1[i].y, a1[i >> 1]); AP_PIN(a1[i >> 1]);
+                    a1[i >> 1] = fmaf(w[i].z, q1[i].z, a1[i >> 1]); AP_PIN(a1[i >> 1]);
+                    if (i < 3) { a1[i >> 1] = fmaf(w[i].w, q1[i].w, a1[i >> 1]); AP_PIN(a1[i >> 1]); }
+                }
+                float s0 = fmaf(fz[ps], a0[1], a0[0]);
+                AP_PIN(s0);
+                a1[1] = fmaf(w[3].w, q1[3].w, a1[1]); AP_PIN(a1[1]);
+                *reinterpret_cast<ap_float2 *>(sa[ps]) = ap_mk(s0, fmaf(fz[ps], a1[1], a1[0]));
+                *reinterpret_cast<ap_float2 *>(sb[ps]) = ap_mk(a0[1], a1[1]);
+            }
+            AP_WAVE_SYNC();
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const ap_float2 *pr = reinterpret_cast<const ap_float2 *>(partial + rs0[i]);
+                const ap_float2 p0 = pr[0], p1 = pr[1], p2 = pr[2], p3 = pr[3];
+                float s0 = cnt[i] > 0 ? p0.x : 0.0f, s1 = cnt[i] > 0 ? p0.y : 0.0f;
+                s0 += cnt[i] > 1 ? p1.x : 0.0f; s1 += cnt[i] > 1 ? p1.y : 0.0f;
+                s0 += cnt[i] > 2 ? p2.x : 0.0f; s1 += cnt[i] > 2 ? p2.y : 0.0f;
+                s0 += cnt[i] > 3 ? p3.x : 0.0f; s1 += cnt[i] > 3 ? p3.y : 0.0f;
+                sum0[i] = s0; sum1[i] = s1;
+                vmax = fmaxf(vmax, cnt[i] > 0 ? fmaxf(s0, s1) : vmax);
+            }
+        };
+        // one frame; returns false after the last frame of the stretch.  PAIR: the frames of the even rotations
+        // always leave their plane in the parking area; where the next frame belongs to the same clip and stretch
+        // (`paired`, uniform) they stop there and the odd rotation's body contracts both frames at once.
+        bool paired = false;
+        auto frame = [&](auto rot_tag) __attribute__((always_inline)) -> bool {
+            constexpr int ROT = decltype(rot_tag)::value;
+            constexpr bool FIRST = PAIR && ROT % 2 == 0;
+            const bool clip_ends = t + 1 == Ti;
+            const bool more = f + 1 < f_hi;
+            transform(rot_tag, std::integral_constant<int, FIRST ? 4 * PARKQ : 0>(), clip_ends, more);
+            float sum2[2];
+            if (FIRST) {
+                paired = !clip_ends && more;
+                // (paired: `finish` books the frame with row sums that the second frame's body overwrites before any
+                // store - the frame neither fills a run nor ends anything; an early return here instead cost 12 VGPRs)
+                sum2[0] = sum2[1] = 0.0f;
+                if (!paired) contract(std::integral_constant<int, PARKQ>(), sum2);
+            } else if (PAIR && paired) {
+                float sum0[2];
+                contract_pair(sum0, sum2);
+                if (half) { acc0[4 + (ROT + 3) % 4] = sum0[0]; acc1[4 + (ROT + 3) % 4] = sum0[1]; }   // uniform branch
+                else { acc0[(ROT + 3) % 4] = sum0[0]; acc1[(ROT + 3) % 4] = sum0[1]; }
+                paired = false;
+            } else {
+                contract(std::integral_constant<int, 0>(), sum2);
+            }
+            finish(rot_tag, sum2, clip_ends, more);
             return more;
         };
         if (U == 1) {

@@ -232,6 +232,7 @@ AP_DEV void apm_fill_tables(ap_float2 *tw2, ap_float2 *tw1, ap_float2 *win, cons
         const int l = i / APM_TW_ROW, e = i % APM_TW_ROW;
         tw1[i] = e < 16 ? tw[2 * (4 * e + (l & 3)) * (l >> 2)] : ap_mk(0.0f, 0.0f);
     }
+    if (!win) return;          // the window pairs live in registers: no table
     for (int i = tid; i < APW_NC; i += nt) win[i] = reinterpret_cast<const ap_float2 *>(window)[i];
 }
 

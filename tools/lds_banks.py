@@ -43,7 +43,48 @@ def cycles(kind, addrs, active=None):
     return total
 
 
+def mel_plan_reads(plan, desc, partial_off=1152, slot_bytes=4):
+    """Bank cycles of the filterbank passes of ap_mel2048_run_kernel for a real plan (ap_mel_plan_host): per
+    pass the four plane reads (|X|^p groups gA, gA + 1, gB, gB + 1 of the lane's entry, 16 bytes each), the
+    four weight reads (row i of pass p at quad 256 p + 64 i + lane) and the two partial-sum stores (slots of
+    `slot_bytes` at float offset `partial_off` of the wave's buffer; 8 bytes = the pair contraction).
+    Returns a list of (plane cycles, weight cycles, store cycles) per pass; ideal (16, 16, 4 or 8)."""
+    n_parts, n_slots = int(desc[12]), int(desc[7])
+    parts = np.asarray(plan[desc[11]:desc[11] + 4 * n_parts]).reshape(n_parts, 4)
+    lanes = np.arange(64)
+    out = []
+    for ps in range((n_parts + 63) // 64):
+        d = np.tile(np.array([n_slots, 0, n_slots, 0]), (64, 1))          # idle lanes: group 0, dump slot
+        n = min(64, n_parts - 64 * ps)
+        d[:n] = parts[64 * ps:64 * ps + n]
+        plane = sum(cycles("r128", 16 * (d[:, c] + j)) for c in (1, 3) for j in (0, 1))
+        weights = sum(cycles("r128", 16 * (256 * ps + 64 * i + lanes)) for i in range(4))
+        sb = np.where(d[:, 2] < 0, n_slots, d[:, 2])
+        kind = "w32" if slot_bytes == 4 else "w64"
+        stores = sum(cycles(kind, 4 * partial_off + slot_bytes * s) for s in (d[:, 0], sb))
+        out.append((plane, weights, stores))
+    return out
+
+
+def headline_plan():
+    """The plan of bench.py's headline: Slaney bank, sr 22 050, n_fft 2048, 128 mels (needs the built library)."""
+    import os, sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from mlx_audio_primitives_amd import _extension as _x
+    fb = _x.mel_filterbank_host(22050, 2048, 128)
+    return _x.mel_plan_host(np.ascontiguousarray(fb, np.float32))
+
+
 if __name__ == "__main__":
+    import sys
+    if "--mel-plan" in sys.argv:
+        plan, desc = headline_plan()
+        print(f"headline plan: {desc[12]} entries, {desc[7]} slots, {(desc[12] + 63) // 64} passes")
+        for sb in (4, 8):
+            for ps, (pl, wt, st) in enumerate(mel_plan_reads(plan, desc, slot_bytes=sb)):
+                print(f"  slots of {sb} bytes, pass {ps}: plane reads {pl} (ideal 16)  weight reads {wt} (ideal 16)  "
+                      f"partial stores {st} (ideal {sb})")
+        sys.exit(0)
     lanes = np.arange(64)
     # exchange-1 of the 1024-point wave FFT: rows of 16 complex, padded row stride S (complex)
     for S in (16, 17, 18, 20):
