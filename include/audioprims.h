@@ -783,6 +783,37 @@ int ap_segment_write_f32(const float *ref /*dev*/, const float *data /*dev*/, in
 int ap_segment_lag(const void *in /*dev*/, int64_t B, int64_t n, int64_t t_lag, int elem_bytes, int to_lag, int64_t in_row_stride,
                    void *out /*dev*/, int64_t out_row_stride, void *stream);
 
+/* viterbi / viterbi_discriminative / viterbi_binary (sequence.py): hidden-Markov decoding, the definition of DESIGN.md 9.12
+ * (csrc/kernels_viterbi.h).  Caps: S <= ap_viterbi_max_states() for the dense decode, T <= ap_viterbi_max_steps().
+ * AP_ERR_INVALID: NULL buffers, empty sizes, a stride below the row length, an unknown mode; AP_ERR_UNSUPPORTED: a size
+ * above its cap.  Nothing is allocated and nothing synchronises.
+ *
+ * ap_viterbi_emission_f32: prob (B, S, T) float32, rows row_stride apart (the padding is never read), sequences S rows
+ * apart.  With tiny = FLT_MIN: mode 0: E (B, T, S) = logf(p + tiny); mode 1: the same minus lps[j], lps (S) the float32 log
+ * state priors; mode 2: E (B, T, S, 2) with [.., 1] = logf(p + tiny) - lps[l, 1] and [.., 0] = logf((1 - p) + tiny) - lps[l, 0],
+ * lps (S, 2).  flags (B) int32 is cleared on `stream` and takes bit 0 for a sequence with a NaN or a value outside [0, 1],
+ * bit 1 (mode 1) for one with a column whose sum is not within 1e-8 + 1e-5 of 1.
+ *
+ * ap_viterbi_decode_f32: E (B, T, S), lt (S, S) the float32 log transitions [from, to], li (S) the log initial
+ * distribution.  v_0 = E_0 + li; at step t >= 1 ptr[t, j] is the smallest i that maximises v[i] + lt[i, j] and
+ * v'[j] = E[t, j] + that maximum; after every step, step 0 included, m = max v is subtracted from v and added, in time
+ * order, to a float64 sum.  The last state is the first maximum of the final v, states[t] = ptr[t + 1, states[t + 1]],
+ * logp = the sum + v[states[T - 1]].  ptr (B, T, S) uint16 is scratch the caller provides (row 0 is written as 0),
+ * states (B, T) int32, logp (B) float64.  Every addition is one rounded float32 operation: the outputs depend on nothing
+ * but E, lt and li.
+ *
+ * ap_viterbi_binary_f32: S independent two-state chains per sequence on E (B, T, S, 2): lt (4) shared, or (S, 4) with
+ * per_label, as [from][to]; li (S, 2).  The recursion of the dense decode; bits (B, ceil(T / 16), S) uint32 is scratch
+ * (two pointer bits per step), states (B, S, T) int32, logp (B, S) float64. */
+int ap_viterbi_max_states(void);
+int ap_viterbi_max_steps(void);
+int ap_viterbi_emission_f32(const float *prob /*dev*/, int64_t B, int64_t S, int64_t T, int64_t row_stride, int mode,
+                            const float *lps /*dev or NULL*/, float *E /*dev*/, int32_t *flags /*dev (B)*/, void *stream);
+int ap_viterbi_decode_f32(const float *E /*dev*/, int64_t B, int64_t S, int64_t T, const float *lt /*dev*/, const float *li /*dev*/,
+                          uint16_t *ptr /*dev*/, int32_t *states /*dev*/, double *logp /*dev*/, void *stream);
+int ap_viterbi_binary_f32(const float *E /*dev*/, int64_t B, int64_t S, int64_t T, const float *lt /*dev*/, int per_label,
+                          const float *li /*dev*/, uint32_t *bits /*dev*/, int32_t *states /*dev*/, double *logp /*dev*/, void *stream);
+
 /* piptrack / estimate_tuning / pitch_tuning (pitch.py): the definition of DESIGN.md 9.10 (csrc/kernels_piptrack.h).
  * S: (B, F, T) magnitudes, rows in_row_stride elements apart (>= T; the padding is never read), clips F rows apart;
  * in_kind 0: float32, 1: complex64 as (re, im), |z| = sqrtf(fmaf(im, im, re re)) taken on load.  Per frame, with

@@ -25,6 +25,8 @@ from .pitch import autocorrelation, estimate_tuning, periodicity, piptrack, pitc
 from .resample import resample, resample_poly
 from .rhythm import beat_track, tempo, tempo_frequencies, tempogram
 from .segment import cross_similarity, lag_to_recurrence, recurrence_matrix, recurrence_to_lag
+from .sequence import (transition_cycle, transition_local, transition_loop, transition_uniform, viterbi, viterbi_binary,
+                       viterbi_discriminative)
 from .stft import check_nola, istft, magnitude, phase, set_spectrum_layout, stft, stft_padded_rows
 from .streaming import StreamingISTFT, StreamingPCEN, StreamingSTFT
 from .windows import get_window
@@ -40,7 +42,7 @@ __all__ = [
     "griffinlim", "griffinlim_iter", "resample", "resample_poly",
     "set_spectrum_layout", "stft_padded_rows",
     "spectral_centroid", "spectral_bandwidth", "spectral_rolloff", "spectral_flatness", "spectral_contrast", "spectral_features",
-    "StreamingSTFT", "StreamingISTFT", "autocorrelation", "pitch_detect_acf", "periodicity", "yin", "yin_cmnd", "piptrack", "pitch_tuning", "estimate_tuning", "hpss", "hpss_medians", "hpss_audio", "harmonic", "percussive", "onset_strength", "onset_detect", "peak_pick", "tempogram", "tempo", "tempo_frequencies", "beat_track", "pcen", "StreamingPCEN", "cqt", "vqt", "cqt_frequencies", "chroma_stft", "chroma_cqt", "chroma_cens", "tonnetz", "chroma_filterbank", "cq_to_chroma", "dtw", "dtw_backtracking", "recurrence_matrix", "cross_similarity", "recurrence_to_lag", "lag_to_recurrence", "pcm16_to_float", "hz_to_bark", "bark_to_hz", "bark_filterbank", "linear_filterbank", "filterbank_spectrogram",
+    "StreamingSTFT", "StreamingISTFT", "autocorrelation", "pitch_detect_acf", "periodicity", "yin", "yin_cmnd", "piptrack", "pitch_tuning", "estimate_tuning", "hpss", "hpss_medians", "hpss_audio", "harmonic", "percussive", "onset_strength", "onset_detect", "peak_pick", "tempogram", "tempo", "tempo_frequencies", "beat_track", "pcen", "StreamingPCEN", "cqt", "vqt", "cqt_frequencies", "chroma_stft", "chroma_cqt", "chroma_cens", "tonnetz", "chroma_filterbank", "cq_to_chroma", "dtw", "dtw_backtracking", "recurrence_matrix", "cross_similarity", "recurrence_to_lag", "lag_to_recurrence", "viterbi", "viterbi_discriminative", "viterbi_binary", "transition_uniform", "transition_loop", "transition_cycle", "transition_local", "pcm16_to_float", "hz_to_bark", "bark_to_hz", "bark_filterbank", "linear_filterbank", "filterbank_spectrogram",
     "zero_crossing_rate", "frame", "rms", "preemphasis", "deemphasis", "delta",
     "mfcc", "dct", "power_to_db", "db_to_power", "amplitude_to_db", "db_to_amplitude",
     "validate_positive", "validate_non_negative", "validate_range",

@@ -14,7 +14,7 @@ ROOT = os.path.dirname(PKG_DIR)
 OBJ_DIR = os.path.join(ROOT, "build", "obj")
 # AP_LIB_PATH: load another build of the same sources instead (diagnostic builds, tools/diag_clock.py)
 LIB_PATH = os.environ.get("AP_LIB_PATH") or os.path.join(PKG_DIR, "libaudioprims_hip.so")
-SOURCES = ["audioprims.hip", "stft16.hip", "istft16.hip", "istft_stream.hip", "yin.hip", "hpss.hip", "onset.hip", "rhythm.hip", "pcen.hip", "cqt.hip", "chroma.hip", "dtw.hip", "piptrack.hip", "segment.hip", "host_builders.cpp"]
+SOURCES = ["audioprims.hip", "stft16.hip", "istft16.hip", "istft_stream.hip", "yin.hip", "hpss.hip", "onset.hip", "rhythm.hip", "pcen.hip", "cqt.hip", "chroma.hip", "dtw.hip", "piptrack.hip", "segment.hip", "viterbi.hip", "host_builders.cpp"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 
 

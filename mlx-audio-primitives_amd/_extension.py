@@ -70,6 +70,7 @@ ABI_SYMBOLS = [
     "ap_piptrack_max_bins", "ap_piptrack_max_records", "ap_piptrack_f32", "ap_piptrack_records_f32", "ap_piptrack_tuning_f32",
     "ap_pitch_hist_f32",
     "ap_segment_max_len", "ap_segment_threshold_f32", "ap_segment_bandwidth_f32", "ap_segment_write_f32", "ap_segment_lag",
+    "ap_viterbi_max_states", "ap_viterbi_max_steps", "ap_viterbi_emission_f32", "ap_viterbi_decode_f32", "ap_viterbi_binary_f32",
     "ap_pcm16_to_f32", "ap_melspec_pcm16_fused", "ap_melspec_pcm16_f32",
 ]
 
@@ -179,6 +180,11 @@ def _declare(lib) -> None:
         "ap_segment_bandwidth_f32": [P, L, L, I, P, P],
         "ap_segment_write_f32": [P, P, L, I, L, L, L, L, I, I, L, I, I, I, P, P, ctypes.c_double, P, L, P],
         "ap_segment_lag": [P, L, L, L, I, I, L, P, L, P],
+        "ap_viterbi_max_states": [],
+        "ap_viterbi_max_steps": [],
+        "ap_viterbi_emission_f32": [P, L, L, L, L, I, P, P, P, P],
+        "ap_viterbi_decode_f32": [P, L, L, L, P, P, P, P, P, P],
+        "ap_viterbi_binary_f32": [P, L, L, L, P, I, P, P, P, P, P],
         "ap_pcm16_to_f32": [P, L, F, P, P],
         "ap_melspec_pcm16_fused": [L, I, I, I, I, I, F, P],
         "ap_melspec_pcm16_f32": [P, L, L, I, I, P, P, I, I, L, P, P, P, I, F, P, P, P, P],
