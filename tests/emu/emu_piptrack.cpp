@@ -8,7 +8,7 @@
 
 alignas(16) char ap_smem[160 * 1024];
 
-// What the kernels need and the shim lacks: integer atomics (the emulated threads are OS threads), a wave ballot and a
+// What the kernels need and the shim lacks: integer atomics, a wave ballot and a
 // broadcast of lane 0's value, both over the shim's per-wave barrier.
 inline unsigned atomicAdd(unsigned *p, unsigned v) { return __atomic_fetch_add(p, v, __ATOMIC_RELAXED); }
 inline unsigned long long atomicAdd(unsigned long long *p, unsigned long long v) { return __atomic_fetch_add(p, v, __ATOMIC_RELAXED); }

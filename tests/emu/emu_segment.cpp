@@ -6,7 +6,7 @@
 
 alignas(16) char ap_smem[160 * 1024];
 
-// the integer LDS atomic of the histograms (the emulated threads are OS threads)
+// the integer LDS atomic of the histograms
 inline unsigned atomicAdd(unsigned *p, unsigned v) { return __atomic_fetch_add(p, v, __ATOMIC_RELAXED); }
 
 #include "../../mlx-audio-primitives_amd/csrc/kernels_segment.h"

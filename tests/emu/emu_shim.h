@@ -1,9 +1,12 @@
 // TEST INFRASTRUCTURE ONLY — a minimal SIMT emulator so the *same kernel source*
-// (mlx-audio-primitives_amd/csrc/kernels_*.h) can be executed on the CPU: one OS
-// thread per GPU thread of a workgroup, std::barrier for __syncthreads(),
-// workgroups run one after another.  Used by tests/test_emu_kernels.py (and for
-// ASan/UBSan runs, which the GPU pool does not allow).  Never loaded by the
-// product package.
+// (mlx-audio-primitives_amd/csrc/kernels_*.h) can be executed on the CPU: one
+// fiber (ucontext) per GPU thread of a workgroup, all on the calling OS thread and
+// resumed round-robin; __syncthreads() hands over to the next fiber until the whole
+// workgroup has arrived; workgroups run one after another.  (One OS thread per GPU
+// thread with std::barrier computes the same, but each barrier then costs a futex
+// wake-up per thread, which on a virtual machine takes the suite from minutes to
+// hours.)  Used by tests/test_emu_kernels.py (and for ASan/UBSan runs, which the GPU
+// pool does not allow).  Never loaded by the product package.
 //
 // LDS.  Dynamic LDS (`extern __shared__ char ap_smem[]`) is the 160 KB array below, guarded by
 // emu_lds_limit().  `__shared__` itself is defined away, so a STATIC `__shared__ float a[N]` inside a
@@ -18,12 +21,15 @@
 // ap_smem keeps its meaning.  Static arrays have no guard band: a twin that can size a tile checks it
 // against the array bound before it launches.
 #pragma once
-#include <barrier>
+#include <sys/mman.h>
+#include <ucontext.h>
+
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
+#include <cstdlib>
 #include <functional>
 #include <memory>
-#include <thread>
 #include <vector>
 
 struct emu_dim3 {
@@ -32,7 +38,40 @@ struct emu_dim3 {
 
 inline thread_local emu_dim3 threadIdx, blockIdx;
 inline emu_dim3 blockDim, gridDim;
-inline std::barrier<> *emu_barrier_ptr = nullptr;
+
+// ---- fibers: the GPU threads of the running workgroup -----
+struct emu_barrier {                  // `need` fibers arrive, then all of them go on
+    unsigned need = 0, arrived = 0, generation = 0;
+};
+constexpr size_t EMU_STACK_BYTES = size_t(1) << 20;       // per fiber; pages are committed when touched
+inline ucontext_t emu_scheduler_ctx;
+inline std::vector<ucontext_t> emu_fiber_ctx;
+inline std::vector<unsigned char> emu_fiber_done;
+inline unsigned emu_fiber_cur = 0;
+inline std::function<void(unsigned)> emu_fiber_body;
+inline char *emu_stacks = nullptr;
+inline size_t emu_stacks_fibers = 0;
+inline emu_barrier emu_block_barrier, emu_wave_barriers[16];
+
+inline void emu_yield() {             // threadIdx / blockIdx are the running fiber's: carry them across
+    const emu_dim3 t = threadIdx, b = blockIdx;
+    swapcontext(&emu_fiber_ctx[emu_fiber_cur], &emu_scheduler_ctx);
+    threadIdx = t;
+    blockIdx = b;
+}
+inline void emu_arrive_and_wait(emu_barrier &bar) {
+    const unsigned g = bar.generation;
+    if (++bar.arrived == bar.need) {
+        bar.arrived = 0;
+        ++bar.generation;
+        return;
+    }
+    while (bar.generation == g) emu_yield();
+}
+inline void emu_fiber_entry() {
+    emu_fiber_body(emu_fiber_cur);
+    emu_fiber_done[emu_fiber_cur] = 1;                    // uc_link returns to the scheduler
+}
 
 #define __global__
 #define __device__
@@ -45,9 +84,8 @@ inline std::barrier<> *emu_barrier_ptr = nullptr;
 
 // ---- wave-level helpers used by kernels_wave.h: wave w = threads [64w, 64w+64) -----
 inline float emu_xchg[1024];
-inline std::barrier<> *emu_wave_barriers[16];
-inline void __syncthreads() { emu_barrier_ptr->arrive_and_wait(); }
-inline void emu_wave_sync() { emu_wave_barriers[threadIdx.x >> 6]->arrive_and_wait(); }
+inline void __syncthreads() { emu_arrive_and_wait(emu_block_barrier); }
+inline void emu_wave_sync() { emu_arrive_and_wait(emu_wave_barriers[threadIdx.x >> 6]); }
 inline float emu_lane_xor(float x, int mask) {
     emu_xchg[threadIdx.x] = x;
     emu_wave_sync();
@@ -85,28 +123,47 @@ void emu_launch(unsigned grid, unsigned block, F &&body) {
         for (int i = guard_from; i < 160 * 1024; ++i) ap_smem[i] = (char)0xA5;
     gridDim.x = grid;
     blockDim.x = block;
-    std::barrier<> bar((std::ptrdiff_t)block);
-    emu_barrier_ptr = &bar;
-    std::vector<std::unique_ptr<std::barrier<>>> wbars;
-    for (unsigned w = 0; w * 64 < block; ++w) {
-        const unsigned n = block - w * 64 < 64 ? block - w * 64 : 64;
-        wbars.emplace_back(new std::barrier<>((std::ptrdiff_t)n));
-        emu_wave_barriers[w] = wbars.back().get();
+    if (block > emu_stacks_fibers) {
+        if (emu_stacks) munmap(emu_stacks, emu_stacks_fibers * EMU_STACK_BYTES);
+        void *m = mmap(nullptr, block * EMU_STACK_BYTES, PROT_READ | PROT_WRITE,
+                       MAP_PRIVATE | MAP_ANONYMOUS | MAP_NORESERVE, -1, 0);
+        if (m == MAP_FAILED) abort();
+        emu_stacks = (char *)m;
+        emu_stacks_fibers = block;
+        for (unsigned t = 0; t < block; ++t)          // lowest page of every stack: an overflow faults, not corrupts
+            mprotect(emu_stacks + t * EMU_STACK_BYTES, 4096, PROT_NONE);
     }
-    std::vector<std::thread> threads;
-    threads.reserve(block);
+    emu_block_barrier = emu_barrier{block, 0, 0};
+    for (unsigned w = 0; w * 64 < block; ++w)
+        emu_wave_barriers[w] = emu_barrier{block - w * 64 < 64 ? block - w * 64 : 64, 0, 0};
+    emu_fiber_body = [&](unsigned t) {
+        threadIdx.x = t;
+        for (unsigned b = 0; b < grid; ++b) {
+            blockIdx.x = b;
+            body();
+            emu_arrive_and_wait(emu_block_barrier);   // workgroups of one launch share ap_smem
+        }
+    };
+    emu_fiber_ctx.assign(block, ucontext_t{});
+    emu_fiber_done.assign(block, 0);
     for (unsigned t = 0; t < block; ++t) {
-        threads.emplace_back([&, t]() {
-            threadIdx.x = t;
-            for (unsigned b = 0; b < grid; ++b) {
-                blockIdx.x = b;
-                body();
-                bar.arrive_and_wait();   // workgroups of one launch share ap_smem
-            }
-        });
+        getcontext(&emu_fiber_ctx[t]);
+        emu_fiber_ctx[t].uc_stack.ss_sp = emu_stacks + t * EMU_STACK_BYTES;
+        emu_fiber_ctx[t].uc_stack.ss_size = EMU_STACK_BYTES;
+        emu_fiber_ctx[t].uc_link = &emu_scheduler_ctx;
+        makecontext(&emu_fiber_ctx[t], emu_fiber_entry, 0);
     }
-    for (auto &th : threads) th.join();
-    emu_barrier_ptr = nullptr;
+    const emu_dim3 t0 = threadIdx, b0 = blockIdx;
+    for (unsigned left = block; left > 0;)
+        for (unsigned t = 0; t < block; ++t)
+            if (!emu_fiber_done[t]) {
+                emu_fiber_cur = t;
+                swapcontext(&emu_scheduler_ctx, &emu_fiber_ctx[t]);
+                left -= emu_fiber_done[t];
+            }
+    threadIdx = t0;
+    blockIdx = b0;
+    emu_fiber_body = nullptr;
     if (guard_from > 0)
         for (int i = guard_from; i < 160 * 1024; ++i)
             if (ap_smem[i] != (char)0xA5) { ++emu_lds_overruns; break; }
