@@ -814,6 +814,27 @@ int ap_viterbi_decode_f32(const float *E /*dev*/, int64_t B, int64_t S, int64_t 
 int ap_viterbi_binary_f32(const float *E /*dev*/, int64_t B, int64_t S, int64_t T, const float *lt /*dev*/, int per_label,
                           const float *li /*dev*/, uint32_t *bits /*dev*/, int32_t *states /*dev*/, double *logp /*dev*/, void *stream);
 
+/* nmf / decompose (decompose.py): non-negative matrix factorisation by multiplicative updates, the definition of DESIGN.md
+ * 9.13 (csrc/kernels_nmf.h).  V (B, F, T) float32 >= 0, rows row_stride elements apart (>= T; the padding is never read),
+ * W (B, F, K), H (B, K, T) dense, 1 <= K <= ap_nmf_max_components().  beta_loss 0 (Frobenius) / 1 (Kullback-Leibler).
+ *
+ * ap_nmf_mu_f32 enqueues n_iter iterations on `stream`, each "update H, then W with the new H" (update_w = 0: W is held):
+ *   0:  H <- H * (W^T V) / ((W^T W) H + eps)                   W <- W * (V H^T) / (W (H H^T) + eps)
+ *   1:  H <- H * (W^T (V / (W H + eps))) / (W^T 1 + eps)       W <- W * ((V / (W H + eps)) H^T) / (1 H^T + eps)
+ * in place, every contraction on the float32 matrix cores, every sum in one fixed order (the same bits on every run).
+ * ap_nmf_objective_f32 stores per item ||V - W H||_F^2 (0) or sum V log(V / (W H + eps)) - V + W H with 0 log 0 = 0 (1),
+ * the elements and their sum in float64.  `workspace`: ap_nmf_workspace_bytes(...) bytes of device memory, 8-byte aligned
+ * (0 for sizes that are refused).  Nothing is allocated and nothing synchronises.  AP_ERR_INVALID: NULL buffers, empty
+ * sizes, K out of range, row_stride < T, an unknown loss, eps <= 0, n_iter < 0; AP_ERR_UNSUPPORTED: more than 2^31 - 1
+ * tiles of 64 rows or columns. */
+int ap_nmf_max_components(void);
+int64_t ap_nmf_workspace_bytes(int64_t B, int64_t F, int64_t T, int K, int beta_loss);
+int ap_nmf_mu_f32(const float *V /*dev*/, int64_t B, int64_t F, int64_t T, int64_t row_stride, int K, float *W /*dev*/, float *H /*dev*/,
+                  int n_iter, int beta_loss, int update_w, float eps, void *workspace /*dev*/, void *stream);
+int ap_nmf_objective_f32(const float *V /*dev*/, int64_t B, int64_t F, int64_t T, int64_t row_stride, int K, const float *W /*dev*/,
+                         const float *H /*dev*/, int beta_loss, float eps, double *out_f64 /*dev (B)*/, void *workspace /*dev*/,
+                         void *stream);
+
 /* piptrack / estimate_tuning / pitch_tuning (pitch.py): the definition of DESIGN.md 9.10 (csrc/kernels_piptrack.h).
  * S: (B, F, T) magnitudes, rows in_row_stride elements apart (>= T; the padding is never read), clips F rows apart;
  * in_kind 0: float32, 1: complex64 as (re, im), |z| = sqrtf(fmaf(im, im, re re)) taken on load.  Per frame, with

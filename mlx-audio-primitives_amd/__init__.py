@@ -11,7 +11,7 @@ from .convert import amplitude_to_db, db_to_amplitude, db_to_power, power_to_db
 from .chroma import chroma_cens, chroma_cqt, chroma_filterbank, chroma_stft, cq_to_chroma, tonnetz
 from .cqt import cqt, cqt_frequencies, vqt
 from .dtw import dtw, dtw_backtracking
-from .decompose import harmonic, hpss, hpss_audio, hpss_medians, percussive
+from .decompose import harmonic, hpss, hpss_audio, hpss_medians, nmf, percussive
 from .features import (spectral_bandwidth, spectral_centroid, spectral_contrast, spectral_features, spectral_flatness,
                        spectral_rolloff, zero_crossing_rate)
 from .filterbanks import bark_filterbank, bark_to_hz, hz_to_bark, linear_filterbank
@@ -42,7 +42,7 @@ __all__ = [
     "griffinlim", "griffinlim_iter", "resample", "resample_poly",
     "set_spectrum_layout", "stft_padded_rows",
     "spectral_centroid", "spectral_bandwidth", "spectral_rolloff", "spectral_flatness", "spectral_contrast", "spectral_features",
-    "StreamingSTFT", "StreamingISTFT", "autocorrelation", "pitch_detect_acf", "periodicity", "yin", "yin_cmnd", "piptrack", "pitch_tuning", "estimate_tuning", "hpss", "hpss_medians", "hpss_audio", "harmonic", "percussive", "onset_strength", "onset_detect", "peak_pick", "tempogram", "tempo", "tempo_frequencies", "beat_track", "pcen", "StreamingPCEN", "cqt", "vqt", "cqt_frequencies", "chroma_stft", "chroma_cqt", "chroma_cens", "tonnetz", "chroma_filterbank", "cq_to_chroma", "dtw", "dtw_backtracking", "recurrence_matrix", "cross_similarity", "recurrence_to_lag", "lag_to_recurrence", "viterbi", "viterbi_discriminative", "viterbi_binary", "transition_uniform", "transition_loop", "transition_cycle", "transition_local", "pcm16_to_float", "hz_to_bark", "bark_to_hz", "bark_filterbank", "linear_filterbank", "filterbank_spectrogram",
+    "StreamingSTFT", "StreamingISTFT", "autocorrelation", "pitch_detect_acf", "periodicity", "yin", "yin_cmnd", "piptrack", "pitch_tuning", "estimate_tuning", "hpss", "hpss_medians", "hpss_audio", "harmonic", "percussive", "nmf", "onset_strength", "onset_detect", "peak_pick", "tempogram", "tempo", "tempo_frequencies", "beat_track", "pcen", "StreamingPCEN", "cqt", "vqt", "cqt_frequencies", "chroma_stft", "chroma_cqt", "chroma_cens", "tonnetz", "chroma_filterbank", "cq_to_chroma", "dtw", "dtw_backtracking", "recurrence_matrix", "cross_similarity", "recurrence_to_lag", "lag_to_recurrence", "viterbi", "viterbi_discriminative", "viterbi_binary", "transition_uniform", "transition_loop", "transition_cycle", "transition_local", "pcm16_to_float", "hz_to_bark", "bark_to_hz", "bark_filterbank", "linear_filterbank", "filterbank_spectrogram",
     "zero_crossing_rate", "frame", "rms", "preemphasis", "deemphasis", "delta",
     "mfcc", "dct", "power_to_db", "db_to_power", "amplitude_to_db", "db_to_amplitude",
     "validate_positive", "validate_non_negative", "validate_range",

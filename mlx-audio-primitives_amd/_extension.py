@@ -71,6 +71,7 @@ ABI_SYMBOLS = [
     "ap_pitch_hist_f32",
     "ap_segment_max_len", "ap_segment_threshold_f32", "ap_segment_bandwidth_f32", "ap_segment_write_f32", "ap_segment_lag",
     "ap_viterbi_max_states", "ap_viterbi_max_steps", "ap_viterbi_emission_f32", "ap_viterbi_decode_f32", "ap_viterbi_binary_f32",
+    "ap_nmf_max_components", "ap_nmf_workspace_bytes", "ap_nmf_mu_f32", "ap_nmf_objective_f32",
     "ap_pcm16_to_f32", "ap_melspec_pcm16_fused", "ap_melspec_pcm16_f32",
 ]
 
@@ -185,6 +186,9 @@ def _declare(lib) -> None:
         "ap_viterbi_emission_f32": [P, L, L, L, L, I, P, P, P, P],
         "ap_viterbi_decode_f32": [P, L, L, L, P, P, P, P, P, P],
         "ap_viterbi_binary_f32": [P, L, L, L, P, I, P, P, P, P, P],
+        "ap_nmf_max_components": [],
+        "ap_nmf_mu_f32": [P, L, L, L, L, I, P, P, I, I, I, F, P, P],
+        "ap_nmf_objective_f32": [P, L, L, L, L, I, P, P, I, F, P, P, P],
         "ap_pcm16_to_f32": [P, L, F, P, P],
         "ap_melspec_pcm16_fused": [L, I, I, I, I, I, F, P],
         "ap_melspec_pcm16_f32": [P, L, L, I, I, P, P, I, I, L, P, P, P, I, F, P, P, P, P],
@@ -206,6 +210,8 @@ def _declare(lib) -> None:
     lib.ap_deemphasis_workspace_floats.restype = L
     lib.ap_tempogram_agg_floats.argtypes = [L, L, I, I]
     lib.ap_tempogram_agg_floats.restype = L
+    lib.ap_nmf_workspace_bytes.argtypes = [L, L, L, I, I]
+    lib.ap_nmf_workspace_bytes.restype = L
     lib.ap_mse_workspace_doubles.argtypes = []
     lib.ap_mse_workspace_doubles.restype = L
 
