@@ -835,6 +835,28 @@ int ap_nmf_objective_f32(const float *V /*dev*/, int64_t B, int64_t F, int64_t T
                          const float *H /*dev*/, int beta_loss, float eps, double *out_f64 /*dev (B)*/, void *workspace /*dev*/,
                          void *stream);
 
+/* mel_to_stft / mel_to_audio (inverse.py): non-negative least squares per frame, min_x ||A x - s||^2 with x >= 0, by
+ * accelerated projected gradient with a fixed step and a fixed iteration count, the definition of DESIGN.md 9.14
+ * (csrc/kernels_nnls.h), one launch.  s (B, M, T) float32 >= 0, rows row_stride elements apart (>= T; the padding is
+ * never read); A the non-negative (M, F) bank, handed over as the plan ap_nnls_plan_host builds from it (copy it to the
+ * device: the band of every row, the row range of every bin, the weights of both; ap_nnls_plan_words int32 words, 0 for
+ * bad arguments); P (F, M) the initial-solution matrix (pinv(A)); step = 1 / lambda_max(A A^T); momentum (n_iter) the
+ * coefficients (t - 1) / t' of t' = (1 + sqrt(1 + 4 t^2)) / 2 from t = 1 (may be NULL when n_iter = 0):
+ *   x0 = max(P s, 0); z = x0;  n_iter times: r = A z - s; x' = max(z - step A^T r, 0); z = x' + momentum[i] (x' - x); x = x'
+ *   out = x^(1 / power)   (power 1: x, power 2: sqrtf(x)),  (B, F, T) with rows out_row_stride apart (the padding is
+ *   never written)
+ * Every sum runs in one fixed order: the same bits on every run and for a clip alone or inside a batch.  A plan whose
+ * header does not say (M, F) is not used (nothing is written).  AP_ERR_INVALID: NULL buffers, empty sizes, strides < T,
+ * n_iter < 0, power or step not positive and finite, a bank with a negative or non-finite entry (plan);
+ * AP_ERR_UNSUPPORTED: F > ap_nnls_max_bins(), M > ap_nnls_max_rows(), more than 2^31 - 1 tiles of 16 frames. */
+int ap_nnls_max_bins(void);
+int ap_nnls_max_rows(void);
+int64_t ap_nnls_plan_words(const float *fb_host /*(M,F)*/, int n_rows, int n_bins);
+int ap_nnls_plan_host(const float *fb_host /*(M,F)*/, int n_rows, int n_bins, int32_t *plan_host);
+int ap_nnls_fista_f32(const float *s /*dev*/, int64_t B, int M, int F, int64_t T, int64_t row_stride, const int32_t *A_plan /*dev*/,
+                      const float *P /*dev (F,M)*/, float step, const float *momentum /*dev (n_iter)*/, int n_iter, float power,
+                      float *out /*dev*/, int64_t out_row_stride, void *stream);
+
 /* piptrack / estimate_tuning / pitch_tuning (pitch.py): the definition of DESIGN.md 9.10 (csrc/kernels_piptrack.h).
  * S: (B, F, T) magnitudes, rows in_row_stride elements apart (>= T; the padding is never read), clips F rows apart;
  * in_kind 0: float32, 1: complex64 as (re, im), |z| = sqrtf(fmaf(im, im, re re)) taken on load.  Per frame, with

@@ -17,6 +17,7 @@ from .features import (spectral_bandwidth, spectral_centroid, spectral_contrast,
 from .filterbanks import bark_filterbank, bark_to_hz, hz_to_bark, linear_filterbank
 from .framing import deemphasis, frame, preemphasis, rms
 from .griffinlim import griffinlim, griffinlim_iter
+from .inverse import mel_to_audio, mel_to_stft, mfcc_to_audio, mfcc_to_mel
 from .mel import filterbank_spectrogram, hz_to_mel, mel_filterbank, mel_to_hz, melspectrogram, pcm16_to_float
 from .mfcc import dct, delta, mfcc
 from .onset import onset_detect, onset_strength, peak_pick
@@ -45,5 +46,6 @@ __all__ = [
     "StreamingSTFT", "StreamingISTFT", "autocorrelation", "pitch_detect_acf", "periodicity", "yin", "yin_cmnd", "piptrack", "pitch_tuning", "estimate_tuning", "hpss", "hpss_medians", "hpss_audio", "harmonic", "percussive", "nmf", "onset_strength", "onset_detect", "peak_pick", "tempogram", "tempo", "tempo_frequencies", "beat_track", "pcen", "StreamingPCEN", "cqt", "vqt", "cqt_frequencies", "chroma_stft", "chroma_cqt", "chroma_cens", "tonnetz", "chroma_filterbank", "cq_to_chroma", "dtw", "dtw_backtracking", "recurrence_matrix", "cross_similarity", "recurrence_to_lag", "lag_to_recurrence", "viterbi", "viterbi_discriminative", "viterbi_binary", "transition_uniform", "transition_loop", "transition_cycle", "transition_local", "pcm16_to_float", "hz_to_bark", "bark_to_hz", "bark_filterbank", "linear_filterbank", "filterbank_spectrogram",
     "zero_crossing_rate", "frame", "rms", "preemphasis", "deemphasis", "delta",
     "mfcc", "dct", "power_to_db", "db_to_power", "amplitude_to_db", "db_to_amplitude",
+    "mel_to_stft", "mel_to_audio", "mfcc_to_mel", "mfcc_to_audio",
     "validate_positive", "validate_non_negative", "validate_range",
 ]

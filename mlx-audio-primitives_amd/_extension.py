@@ -72,6 +72,7 @@ ABI_SYMBOLS = [
     "ap_segment_max_len", "ap_segment_threshold_f32", "ap_segment_bandwidth_f32", "ap_segment_write_f32", "ap_segment_lag",
     "ap_viterbi_max_states", "ap_viterbi_max_steps", "ap_viterbi_emission_f32", "ap_viterbi_decode_f32", "ap_viterbi_binary_f32",
     "ap_nmf_max_components", "ap_nmf_workspace_bytes", "ap_nmf_mu_f32", "ap_nmf_objective_f32",
+    "ap_nnls_max_bins", "ap_nnls_max_rows", "ap_nnls_plan_words", "ap_nnls_plan_host", "ap_nnls_fista_f32",
     "ap_pcm16_to_f32", "ap_melspec_pcm16_fused", "ap_melspec_pcm16_f32",
 ]
 
@@ -189,6 +190,10 @@ def _declare(lib) -> None:
         "ap_nmf_max_components": [],
         "ap_nmf_mu_f32": [P, L, L, L, L, I, P, P, I, I, I, F, P, P],
         "ap_nmf_objective_f32": [P, L, L, L, L, I, P, P, I, F, P, P, P],
+        "ap_nnls_max_bins": [],
+        "ap_nnls_max_rows": [],
+        "ap_nnls_plan_host": [P, I, I, P],
+        "ap_nnls_fista_f32": [P, L, I, I, L, L, P, P, F, P, I, F, P, L, P],
         "ap_pcm16_to_f32": [P, L, F, P, P],
         "ap_melspec_pcm16_fused": [L, I, I, I, I, I, F, P],
         "ap_melspec_pcm16_f32": [P, L, L, I, I, P, P, I, I, L, P, P, P, I, F, P, P, P, P],
@@ -212,6 +217,8 @@ def _declare(lib) -> None:
     lib.ap_tempogram_agg_floats.restype = L
     lib.ap_nmf_workspace_bytes.argtypes = [L, L, L, I, I]
     lib.ap_nmf_workspace_bytes.restype = L
+    lib.ap_nnls_plan_words.argtypes = [P, I, I]
+    lib.ap_nnls_plan_words.restype = L
     lib.ap_mse_workspace_doubles.argtypes = []
     lib.ap_mse_workspace_doubles.restype = L
 
@@ -395,6 +402,15 @@ def mel_plan_host(fb: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
     desc = np.zeros(16, np.int32)
     check(lib().ap_mel_plan_host(fb.ctypes.data, M, F, plan.ctypes.data, desc.ctypes.data))
     return plan, desc
+
+
+def nnls_plan_host(fb: np.ndarray) -> np.ndarray:
+    """Band plan of a non-negative (M, F) bank for ap_nnls_fista_f32 (include/audioprims.h: ap_nnls_plan_host), int32."""
+    fb = np.ascontiguousarray(fb, dtype=np.float32)
+    M, F = fb.shape
+    plan = np.zeros(max(int(lib().ap_nnls_plan_words(fb.ctypes.data, M, F)), 8), np.int32)
+    check(lib().ap_nnls_plan_host(fb.ctypes.data, M, F, plan.ctypes.data))
+    return plan
 
 
 def dct_matrix_host(n_out: int, n_in: int, norm: str | None = "ortho") -> np.ndarray:

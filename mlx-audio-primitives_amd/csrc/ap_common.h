@@ -184,6 +184,15 @@ struct ApIrfftParams {
     ApTile tile;
 };
 
+// NNLS plan of a non-negative (M, F) bank (ap_nnls_plan_host, kernels_nnls.h), int32 words; weights are float bits.
+//   [0] M   [1] F   [2] off rows[M][3]: first column, length, weight offset of the row's band [lo, lo + len)
+//   [3] off bins[F][3]: first row, length, weight offset of the bin's row range   [4] off row weights, row by row
+//   [5] off bin weights, bin by bin   [6] words in all   [7] 0
+// A band runs from the first to the last non-zero of its row (column); zeros inside it are stored, none outside it.
+#define AP_NNLS_HDR 8
+#define AP_NNLS_MAX_BINS 1025      // (2 F + 2 M) 16 floats of LDS: 1025 + 255 = 1280 -> exactly AP_LDS_MAX
+#define AP_NNLS_MAX_ROWS 255
+
 static inline int64_t ap_n_frames(int64_t L, int n_fft, int hop, int center) {
     int64_t Lp = L + (center ? 2 * (int64_t)(n_fft / 2) : 0);
     if (Lp < n_fft) return 0;

@@ -531,4 +531,60 @@ int ap_fft_supported(int n_fft) {
     return 1;
 }
 
+// NNLS plan (ap_common.h: AP_NNLS_HDR): the band of every row and the row range of every bin of a non-negative bank
+// (first to last non-zero, empty when there is none), and the weights of both, packed.
+namespace {
+// first and one-past-last non-zero of the n values at fb[0], fb[stride], ..; (0, 0) when all are zero
+void nnls_span(const float *fb, int n, int64_t stride, int *lo, int *len) {
+    int a = 0, b = n;
+    while (a < n && fb[a * stride] == 0.0f) ++a;
+    while (b > a && fb[(b - 1) * stride] == 0.0f) --b;
+    *lo = a < n ? a : 0;
+    *len = b - a;
+}
+}  // namespace
+
+int64_t ap_nnls_plan_words(const float *fb, int n_rows, int n_bins) {
+    if (!fb || n_rows <= 0 || n_bins <= 0) return 0;
+    int64_t words = AP_NNLS_HDR + 3 * ((int64_t)n_rows + n_bins);
+    int lo, len;
+    for (int m = 0; m < n_rows; ++m) { nnls_span(fb + (int64_t)m * n_bins, n_bins, 1, &lo, &len); words += len; }
+    for (int k = 0; k < n_bins; ++k) { nnls_span(fb + k, n_rows, n_bins, &lo, &len); words += len; }
+    return words;
+}
+
+int ap_nnls_plan_host(const float *fb, int n_rows, int n_bins, int32_t *plan) {
+    if (!fb || !plan || n_rows <= 0 || n_bins <= 0) { ap_set_error("nnls plan: bad arguments"); return AP_ERR_INVALID; }
+    if (n_rows > AP_NNLS_MAX_ROWS || n_bins > AP_NNLS_MAX_BINS) {
+        ap_set_error(("nnls plan: a (" + std::to_string(n_rows) + ", " + std::to_string(n_bins) + ") bank is over the limits of " +
+                      std::to_string(AP_NNLS_MAX_ROWS) + " rows and " + std::to_string(AP_NNLS_MAX_BINS) + " bins").c_str());
+        return AP_ERR_UNSUPPORTED;
+    }
+    const int M = n_rows, F = n_bins;
+    for (int64_t i = 0; i < (int64_t)M * F; ++i)
+        if (!(fb[i] >= 0.0f) || !std::isfinite(fb[i])) { ap_set_error("nnls plan: the filterbank must be finite and non-negative"); return AP_ERR_INVALID; }
+    const int64_t off_rows = AP_NNLS_HDR, off_bins = off_rows + 3 * (int64_t)M, off_wr = off_bins + 3 * (int64_t)F;
+    int64_t w = off_wr;
+    for (int m = 0; m < M; ++m) {
+        int lo, len;
+        nnls_span(fb + (int64_t)m * F, F, 1, &lo, &len);
+        int32_t *d = plan + off_rows + 3 * m;
+        d[0] = lo; d[1] = len; d[2] = (int32_t)(w - off_wr);
+        std::memcpy(plan + w, fb + (int64_t)m * F + lo, sizeof(float) * (size_t)len);
+        w += len;
+    }
+    const int64_t off_wc = w;
+    for (int k = 0; k < F; ++k) {
+        int lo, len;
+        nnls_span(fb + k, M, F, &lo, &len);
+        int32_t *d = plan + off_bins + 3 * k;
+        d[0] = lo; d[1] = len; d[2] = (int32_t)(w - off_wc);
+        for (int j = 0; j < len; ++j) std::memcpy(plan + w + j, fb + (int64_t)(lo + j) * F + k, sizeof(float));
+        w += len;
+    }
+    plan[0] = M; plan[1] = F; plan[2] = (int32_t)off_rows; plan[3] = (int32_t)off_bins;
+    plan[4] = (int32_t)off_wr; plan[5] = (int32_t)off_wc; plan[6] = (int32_t)w; plan[7] = 0;
+    return AP_OK;
+}
+
 }  // extern "C"
