@@ -894,6 +894,24 @@ int ap_piptrack_tuning_f32(const float *records /*dev*/, const uint64_t *counter
 int ap_pitch_hist_f32(const float *frequencies /*dev*/, int64_t n, double bins_per_octave, const double *edges /*dev (n_bins+1)*/,
                       int n_bins, uint64_t *counts /*dev (n_bins)*/, void *stream);
 
+/* reassigned_spectrogram (reassign.py): the definition of DESIGN.md 9.15 (csrc/kernels_reassign.h), one launch.  y (B, L)
+ * float32; the frames, the padding and T are those of ap_stft_f32.  win_h: the window centre-padded to n_fft; win_dh[i] =
+ * (h[(i+1) mod n] - h[(i-1) mod n]) / 2; win_th[i] = h[i] tau[i], tau = i + 0.5 - n/2 (n even), i - n/2 (n odd).  With the
+ * three STFTs S_h, S_dh, S_th of the same frames:
+ *   mags = |S_h|;  freqs = k sr / n - Im(S_dh / S_h) sr / (2 pi);  times = (t hop + (center ? 0 : n/2)) / sr + Re(S_th / S_h) / sr
+ * freqs and times are NaN where mags < sqrt(ref_power) or |S_h|^2 = 0 (NaN also where NumPy's x / 0 is an infinity); with
+ * AP_REASSIGN_FILL (4) such a value is the bin frequency / the frame time instead; with AP_REASSIGN_CLIP (8) freqs is then
+ * clipped to [0, sr / 2] and times to [0, L / sr] (NaN stays).  flags also says which planes are made: AP_REASSIGN_FREQ (1),
+ * AP_REASSIGN_TIME (2); a plane that is off has freqs (times) and win_dh (win_th) NULL and costs no transform.  Outputs are
+ * (B, n_fft/2+1, T) float32 with rows out_row_stride elements apart (>= T; the padding is never written).  The same bits on
+ * every run and for a clip alone or inside a batch.  AP_ERR_INVALID: NULL buffers, both planes off, a pointer that does
+ * not go with its flag, empty sizes, a T other than ap_stft_f32's, out_row_stride < T, sr not positive, ref_power
+ * negative; AP_ERR_UNSUPPORTED: an n_fft without an FFT plan or whose three windowed frames do not fit LDS. */
+int ap_reassign_f32(const float *y /*dev*/, int64_t B, int64_t L, int n_fft, int hop, const float *win_h /*dev*/,
+                    const float *win_dh /*dev or NULL*/, const float *win_th /*dev or NULL*/, const float *tw /*dev*/, int center,
+                    int pad_mode, int64_t T, double sr, double ref_power, int flags, float *freqs /*dev or NULL*/,
+                    float *times /*dev or NULL*/, float *mags /*dev*/, int64_t out_row_stride, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

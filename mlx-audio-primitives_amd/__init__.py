@@ -22,6 +22,7 @@ from .mel import filterbank_spectrogram, hz_to_mel, mel_filterbank, mel_to_hz, m
 from .mfcc import dct, delta, mfcc
 from .onset import onset_detect, onset_strength, peak_pick
 from .pcen import pcen
+from .reassign import reassigned_spectrogram
 from .pitch import autocorrelation, estimate_tuning, periodicity, piptrack, pitch_detect_acf, pitch_tuning, yin, yin_cmnd
 from .resample import resample, resample_poly
 from .rhythm import beat_track, tempo, tempo_frequencies, tempogram
@@ -47,5 +48,6 @@ __all__ = [
     "zero_crossing_rate", "frame", "rms", "preemphasis", "deemphasis", "delta",
     "mfcc", "dct", "power_to_db", "db_to_power", "amplitude_to_db", "db_to_amplitude",
     "mel_to_stft", "mel_to_audio", "mfcc_to_mel", "mfcc_to_audio",
+    "reassigned_spectrogram",
     "validate_positive", "validate_non_negative", "validate_range",
 ]
