@@ -912,6 +912,23 @@ int ap_reassign_f32(const float *y /*dev*/, int64_t B, int64_t L, int n_fft, int
                     int pad_mode, int64_t T, double sr, double ref_power, int flags, float *freqs /*dev or NULL*/,
                     float *times /*dev or NULL*/, float *mags /*dev*/, int64_t out_row_stride, void *stream);
 
+/* phase_vocoder (effects.py; librosa 0.10's phase_vocoder, DESIGN.md 9.16, csrc/kernels_pv.h).  D: rows complex64 rows of
+ * T columns as (re, im) pairs, row_stride complex values apart (>= T; the padding is never read); columns T and T + 1
+ * read as zero.  For k < T_out, pos = (double)k rate, i = floor(pos), a = pos - i:
+ *   out[k] = ((1 - a) |D[i]| + a |D[i+1]|) P_k,  P_0 = u[0],  P_(k+1) = P_k u[i+1] conj(u[i]),  u[c] = D[c] / |D[c]|
+ * with u = 1 where D is zero (of either sign: -0.0 + 0j counts as zero, where NumPy's angle is pi).  That is librosa's
+ * angle recurrence: its expected phase advance only enters through multiples of 2 pi, so hop_length and n_fft do not
+ * appear.  out: rows of T_out complex64, out_row_stride apart (>= T_out; the padding is never written).
+ * ap_phase_vocoder_frames: T_out = len(np.arange(0, T, rate)) = ceil(T / rate) in float64 (0 for T <= 0; -1 for a rate that
+ * is not positive and finite).  ap_phase_vocoder_waves: the waves per row the launch uses for that many rows of T_out
+ * steps (1, 4 or 16): results are the same bits on every run and for any batch at one value of it.  One launch, no
+ * workspace, no state.  AP_ERR_INVALID: NULL buffers, empty sizes, rate, a T_out other than ap_phase_vocoder_frames',
+ * strides, an output overlapping the input; AP_ERR_UNSUPPORTED: T or T_out beyond 2^28. */
+int64_t ap_phase_vocoder_frames(int64_t T, double rate);
+int ap_phase_vocoder_waves(int64_t rows, int64_t T_out);
+int ap_phase_vocoder_f32(const float *D /*dev*/, int64_t rows, int64_t T, int64_t row_stride, double rate, int64_t T_out,
+                         float *out /*dev*/, int64_t out_row_stride, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

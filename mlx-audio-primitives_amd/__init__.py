@@ -12,6 +12,7 @@ from .chroma import chroma_cens, chroma_cqt, chroma_filterbank, chroma_stft, cq_
 from .cqt import cqt, cqt_frequencies, vqt
 from .dtw import dtw, dtw_backtracking
 from .decompose import harmonic, hpss, hpss_audio, hpss_medians, nmf, percussive
+from .effects import phase_vocoder, pitch_shift, time_stretch
 from .features import (spectral_bandwidth, spectral_centroid, spectral_contrast, spectral_features, spectral_flatness,
                        spectral_rolloff, zero_crossing_rate)
 from .filterbanks import bark_filterbank, bark_to_hz, hz_to_bark, linear_filterbank
@@ -49,5 +50,6 @@ __all__ = [
     "mfcc", "dct", "power_to_db", "db_to_power", "amplitude_to_db", "db_to_amplitude",
     "mel_to_stft", "mel_to_audio", "mfcc_to_mel", "mfcc_to_audio",
     "reassigned_spectrogram",
+    "phase_vocoder", "time_stretch", "pitch_shift",
     "validate_positive", "validate_non_negative", "validate_range",
 ]

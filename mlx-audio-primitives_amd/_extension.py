@@ -74,6 +74,7 @@ ABI_SYMBOLS = [
     "ap_nmf_max_components", "ap_nmf_workspace_bytes", "ap_nmf_mu_f32", "ap_nmf_objective_f32",
     "ap_nnls_max_bins", "ap_nnls_max_rows", "ap_nnls_plan_words", "ap_nnls_plan_host", "ap_nnls_fista_f32",
     "ap_reassign_f32",
+    "ap_phase_vocoder_frames", "ap_phase_vocoder_waves", "ap_phase_vocoder_f32",
     "ap_pcm16_to_f32", "ap_melspec_pcm16_fused", "ap_melspec_pcm16_f32",
 ]
 
@@ -196,6 +197,8 @@ def _declare(lib) -> None:
         "ap_nnls_plan_host": [P, I, I, P],
         "ap_nnls_fista_f32": [P, L, I, I, L, L, P, P, F, P, I, F, P, L, P],
         "ap_reassign_f32": [P, L, L, I, I, P, P, P, P, I, I, L, ctypes.c_double, ctypes.c_double, I, P, P, P, L, P],
+        "ap_phase_vocoder_waves": [L, L],
+        "ap_phase_vocoder_f32": [P, L, L, L, ctypes.c_double, L, P, L, P],
         "ap_pcm16_to_f32": [P, L, F, P, P],
         "ap_melspec_pcm16_fused": [L, I, I, I, I, I, F, P],
         "ap_melspec_pcm16_f32": [P, L, L, I, I, P, P, I, I, L, P, P, P, I, F, P, P, P, P],
@@ -221,6 +224,8 @@ def _declare(lib) -> None:
     lib.ap_nmf_workspace_bytes.restype = L
     lib.ap_nnls_plan_words.argtypes = [P, I, I]
     lib.ap_nnls_plan_words.restype = L
+    lib.ap_phase_vocoder_frames.argtypes = [L, ctypes.c_double]
+    lib.ap_phase_vocoder_frames.restype = L
     lib.ap_mse_workspace_doubles.argtypes = []
     lib.ap_mse_workspace_doubles.restype = L
 
