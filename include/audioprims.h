@@ -814,6 +814,40 @@ int ap_viterbi_decode_f32(const float *E /*dev*/, int64_t B, int64_t S, int64_t 
 int ap_viterbi_binary_f32(const float *E /*dev*/, int64_t B, int64_t S, int64_t T, const float *lt /*dev*/, int per_label,
                           const float *li /*dev*/, uint32_t *bits /*dev*/, int32_t *states /*dev*/, double *logp /*dev*/, void *stream);
 
+/* pyin (pitch.py): probabilistic YIN, the definition of DESIGN.md 9.17 (csrc/kernels_pyin.h).  Caps: n_bins <=
+ * ap_pyin_max_bins(), a transition band of at most ap_pyin_max_width() = 2 half_width + 1 bins, T <= ap_viterbi_max_steps();
+ * above a cap AP_ERR_UNSUPPORTED, AP_ERR_INVALID for NULL buffers and empty or non-positive sizes.  Nothing is allocated
+ * and nothing synchronises.
+ *
+ * ap_pyin_observe_f32: d (B, n_lags, T) the curve of ap_yin_cmnd_f32 for the lags lo .. lo + n_lags - 1.  Troughs: lag
+ * index 0 when d[0] < d[1], the last when below its left neighbour, x between when d[x] < d[x-1] and d[x] <= d[x+1].
+ * Trough i passes threshold c when d_i < thr[c] (float32); with N_c the passing troughs and r_i(c) the rank of i among
+ * them in lag order, p_i = sum_c beta[c] nz[N_c] ea[r_i(c)] over the thresholds it passes (thr, beta (n_thresholds); ea,
+ * nz (n_tab >= (n_lags + 1) / 2 + 1), summed in float64 over c ascending, rounded once), and the first lowest trough takes
+ * no_trough_prob times the beta of the thresholds it misses.  Every trough with p_i > 0 goes to the bin
+ * rint(12 bins_per_semitone log2(f0 / fmin)) clipped to [0, n_bins], f0 = sr / (lag + parabolic shift), in float64; bin
+ * n_bins is dropped and the larger lag wins a shared bin.  voiced_prob (B, T) = the float32 sum of the bins clipped to
+ * [0, 1]; E (B, T, n_bins + 1) = logf(p + FLT_MIN), the last column that of (1 - voiced_prob) / n_bins.
+ *
+ * ap_pyin_decode_f32: Viterbi over the states (a, j), a = 0 voiced / 1 unvoiced, j a bin, numbered a n_bins + j, with the
+ * conventions of ap_viterbi_decode_f32 (renormalisation by max v after every step, float64 sum, first maximum last).
+ * lw (2 half_width + 1): lw[d + half_width] the log window at bin offset d; lz (n_bins) the log row sums; ls (4) the log
+ * switch matrix [a][b]; li the log initial probability; -inf forbids.  v_0 = E_0 + li; x[a,i] = (v[a,i] - m) - lz[i];
+ * c[a,j] = max over i in [j - half_width, j + half_width] (inside the bins) of x[a,i] + lw[j - i], the smallest i first;
+ * v'[b,j] = E + max_a c[a,j] + ls[a][b], block 1 only when greater; the pointer is a n_bins + i.  ptr (B, T, 2 n_bins)
+ * uint16 is scratch of the caller.  states (B, T) int32, logp (B) float64, voiced (B, T) uint8 = state < n_bins,
+ * f0 (B, T) = freq[state mod n_bins] (freq (n_bins)), or `fill` on unvoiced frames when use_fill.  max_blocks > 0 caps
+ * the grid (a workgroup then takes several sequences in turn). */
+int ap_pyin_max_bins(void);
+int ap_pyin_max_width(void);
+int ap_pyin_observe_f32(const float *d /*dev*/, int64_t B, int n_lags, int64_t T, int lo, double sr, double fmin, int bins_per_semitone,
+                        int n_bins, const float *thr /*dev*/, const float *beta /*dev*/, int n_thresholds, const float *ea /*dev*/,
+                        const float *nz /*dev*/, int n_tab, float no_trough_prob, float *E /*dev*/, float *voiced_prob /*dev*/, void *stream);
+int ap_pyin_decode_f32(const float *E /*dev*/, int64_t B, int n_bins, int64_t T, const float *lw /*dev*/, int half_width,
+                       const float *lz /*dev*/, const float *ls /*dev*/, float li, const float *freq /*dev*/, int use_fill, float fill,
+                       uint16_t *ptr /*dev*/, int32_t *states /*dev*/, float *f0 /*dev*/, uint8_t *voiced /*dev*/, double *logp /*dev*/,
+                       int max_blocks, void *stream);
+
 /* nmf / decompose (decompose.py): non-negative matrix factorisation by multiplicative updates, the definition of DESIGN.md
  * 9.13 (csrc/kernels_nmf.h).  V (B, F, T) float32 >= 0, rows row_stride elements apart (>= T; the padding is never read),
  * W (B, F, K), H (B, K, T) dense, 1 <= K <= ap_nmf_max_components().  beta_loss 0 (Frobenius) / 1 (Kullback-Leibler).

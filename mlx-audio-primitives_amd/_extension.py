@@ -58,6 +58,7 @@ ABI_SYMBOLS = [
     "ap_spectral_stats_f32", "ap_spectral_audio_fused", "ap_spectral_audio_f32", "ap_spectral_contrast_f32", "ap_frame_stats_f32", "ap_preemphasis_f32", "ap_deemphasis_f32", "ap_deemphasis_workspace_floats", "ap_deemphasis_ws_f32", "ap_savgol_f32",
     "ap_autocorrelation_nfft", "ap_autocorrelation_f32", "ap_acf_peaks_f32",
     "ap_yin_fused", "ap_yin_f32", "ap_yin_cmnd_f32",
+    "ap_pyin_max_bins", "ap_pyin_max_width", "ap_pyin_observe_f32", "ap_pyin_decode_f32",
     "ap_hpss_fused", "ap_hpss_f32",
     "ap_onset_strength_f32", "ap_peak_pick_max_frames", "ap_peak_pick_f32",
     "ap_tempogram_max_win", "ap_tempogram_fused", "ap_tempogram_agg_floats", "ap_tempogram_f32", "ap_tempo_pick_f32",
@@ -147,6 +148,10 @@ def _declare(lib) -> None:
         "ap_yin_fused": [I, I, L],
         "ap_yin_f32": [P, L, L, I, I, I, I, I, F, F, P, P, P, P],
         "ap_yin_cmnd_f32": [P, L, L, I, I, I, I, I, P, P, P],
+        "ap_pyin_max_bins": [],
+        "ap_pyin_max_width": [],
+        "ap_pyin_observe_f32": [P, L, I, L, I, ctypes.c_double, ctypes.c_double, I, I, P, P, I, P, P, I, F, P, P, P],
+        "ap_pyin_decode_f32": [P, L, I, L, P, I, P, P, F, P, I, F, P, P, P, P, P, I, P],
         "ap_hpss_fused": [I, I],
         "ap_hpss_f32": [P, I, L, L, L, L, I, I, F, F, F, I, I, P, P, L, P],
         "ap_onset_strength_f32": [P, L, L, L, L, P, L, I, I, I, I, F, F, F, F, P, P, L, P],

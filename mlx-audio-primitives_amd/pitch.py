@@ -10,6 +10,9 @@ yin / yin_cmnd (no counterpart in the reference; librosa's signature): the YIN f
 cumulative-mean-normalised difference curve on the fused wave-per-frame kernel of csrc/kernels_yin.h
 (frame_length 2048 / 1024) or its direct-sum general kernel.
 
+pyin (no counterpart in the reference; librosa's signature): probabilistic YIN on that curve: an observation kernel and
+a banded voiced / unvoiced Viterbi decode (csrc/kernels_pyin.h).
+
 piptrack / estimate_tuning / pitch_tuning (no counterpart in the reference; librosa's signatures): parabolically
 interpolated STFT peaks on one kernel that reads stft's rows in place, and the tuning they favour from a compact
 record buffer, an exact median by radix select and an integer histogram (csrc/kernels_piptrack.h).
@@ -123,8 +126,8 @@ def periodicity(y, sr: int = 22050, fmin: float = 50.0, fmax: float = 2000.0, fr
     return per[0] if one_d else per
 
 
-def _yin_setup(y, fmin, fmax, sr, frame_length, hop_length, center, pad_mode, who):
-    """Validation, lag range and device input shared by yin / yin_cmnd: (y (B, L), one_d, lo, hi, hop, center)."""
+def _yin_lags(fmin, fmax, sr, frame_length, hop_length, pad_mode, who):
+    """The scalar half of _yin_setup (no device): validation and (lo, hi, hop)."""
     import math
 
     from ._validation import validate_positive
@@ -147,6 +150,12 @@ def _yin_setup(y, fmin, fmax, sr, frame_length, hop_length, center, pad_mode, wh
     if lo >= hi:
         raise ValueError(f"{who}: no lags between sr / fmax and sr / fmin inside the frame (lo = {lo}, hi = {hi}); "
                          "lower fmin, raise fmax or use a longer frame_length")
+    return lo, hi, int(hop_length)
+
+
+def _yin_setup(y, fmin, fmax, sr, frame_length, hop_length, center, pad_mode, who):
+    """Validation, lag range and device input shared by yin / yin_cmnd / pyin: (y (B, L), one_d, lo, hi, hop, center)."""
+    lo, hi, hop_length = _yin_lags(fmin, fmax, sr, frame_length, hop_length, pad_mode, who)
     ndim, L = len(y.shape), (y.shape[-1] if len(y.shape) else 0)
     if ndim not in (1, 2):
         raise ValueError(f"y must be 1D or 2D, got {ndim}D")
@@ -227,6 +236,166 @@ def yin_cmnd(y, *, fmin, fmax, sr: float = 22050, frame_length: int = 2048, hop_
         _yin_call("ap_yin_cmnd_f32", y, frame_length, hop,
                   lambda tw: (_x.ptr(y), B, L, frame_length, hop, int(center), lo, hi, tw, _x.ptr(out), st))
     return out[0] if one_d else out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# pyin (csrc/kernels_pyin.h; librosa 0.10's signature)
+# ---------------------------------------------------------------------------------------------------------------------
+_pyin_cache: dict[str, dict] = {}          # host tables under their parameters (bounded, oldest out first)
+
+
+def _beta_cdf(x, a: int, b: int):
+    """The regularised incomplete beta function for positive integers a, b: the closed binomial sum
+    I_x(a, b) = sum_(j = a .. a + b - 1) C(a + b - 1, j) x^j (1 - x)^(a + b - 1 - j), float64."""
+    import math
+
+    import numpy as np
+
+    x = np.asarray(x, np.float64)
+    m = a + b - 1
+    return sum(math.comb(m, j) * x ** j * (1.0 - x) ** (m - j) for j in range(a, m + 1))
+
+
+def _pyin_tables(*, fmin, fmax, sr, hop, n_lags, n_thresholds=100, beta_parameters=(2, 18), boltzmann_parameter=2, resolution=0.1,
+                 max_transition_rate=35.92, switch_prob=0.01):
+    """Validated host tables of pyin, float64 rounded to float32: a dict with n_bins, bps, W, h and
+    thr, beta (n_thresholds), ea, nz ((n_lags + 1) // 2 + 1), lw (2 h + 1), lz (n_bins), ls (4), li, freq (n_bins)."""
+    import math
+
+    import numpy as np
+
+    from .cqt import _is_real
+    from .onset import _is_int
+
+    key = repr((fmin, fmax, sr, hop, n_lags, n_thresholds, beta_parameters, boltzmann_parameter, resolution, max_transition_rate, switch_prob))
+    if key in _pyin_cache:
+        return _pyin_cache[key]
+    if not _is_int(n_thresholds) or n_thresholds < 1:
+        raise ValueError(f"n_thresholds must be a positive integer, got {n_thresholds!r}")
+    bp = tuple(beta_parameters) if isinstance(beta_parameters, (tuple, list)) else ()
+    if len(bp) != 2 or not all(_is_int(v) and v >= 1 for v in bp):
+        raise ValueError(f"beta_parameters must be two positive integers (the beta CDF is built as a binomial sum), got {beta_parameters!r}")
+    if not _is_real(boltzmann_parameter) or not float(boltzmann_parameter) > 0.0:
+        raise ValueError(f"boltzmann_parameter must be positive, got {boltzmann_parameter!r}")
+    if not _is_real(resolution) or not 0.0 < float(resolution) < 1.0:
+        raise ValueError(f"resolution must lie in (0, 1), got {resolution!r}")
+    if not _is_real(switch_prob) or not 0.0 <= float(switch_prob) <= 1.0:
+        raise ValueError(f"switch_prob must lie in [0, 1], got {switch_prob!r}")
+    if not _is_real(max_transition_rate) or not float(max_transition_rate) >= 0.0:
+        raise ValueError(f"max_transition_rate must be non-negative, got {max_transition_rate!r}")
+    n = int(n_thresholds)
+    bps = int(math.ceil(1.0 / float(resolution)))
+    n_bins = int(math.floor(12 * bps * math.log2(float(fmax) / float(fmin)))) + 1
+    W = int(round(float(max_transition_rate) * 12 * hop / float(sr))) * bps + 1
+    if n_bins < 2 or W > n_bins:
+        raise ValueError(f"the transition width {W} (max_transition_rate over one hop, in bins) must not exceed n_bins = {n_bins} "
+                         "(at least 2); lower max_transition_rate or hop_length, or widen fmin .. fmax")
+    edges = np.arange(n + 1, dtype=np.float64) / n
+    beta = np.maximum(np.diff(_beta_cdf(edges, int(bp[0]), int(bp[1]))), 0.0)
+    lam = float(boltzmann_parameter)
+    k = np.arange((n_lags + 1) // 2 + 1, dtype=np.float64)
+    nz = np.zeros_like(k)
+    nz[1:] = (1.0 - math.exp(-lam)) / (1.0 - np.exp(-lam * k[1:]))
+    lw, lz, ls = _pyin_band(n_bins, W, float(switch_prob))
+    freq = float(fmin) * 2.0 ** (np.arange(n_bins) / (12.0 * bps))
+    if len(_pyin_cache) >= 32:
+        _pyin_cache.pop(next(iter(_pyin_cache)))
+    _pyin_cache[key] = dict(n_bins=n_bins, bps=bps, W=W, h=W // 2, thr=_f32(edges[1:]), beta=_f32(beta), ea=_f32(np.exp(-lam * k)),
+                            nz=_f32(nz), lw=lw, lz=lz, ls=ls, li=float(np.float32(math.log(1.0 / (2 * n_bins)))), freq=_f32(freq))
+    return _pyin_cache[key]
+
+
+def _f32(a):
+    import numpy as np
+
+    return np.ascontiguousarray(np.asarray(a, np.float64).astype(np.float32))
+
+
+def _pyin_band(n_bins: int, W: int, switch_prob: float):
+    """(lw (2 h + 1), lz (n_bins), ls (4)) float32, h = W // 2: row i of transition_local(n_bins, W, window="triangle") is
+    u[j - i] / z_i on the kept band |j - i| <= h, u the window where that function's roll puts it (an even window leaves
+    one end of the band empty), z_i the sum of the row's kept entries; lw = log u, lz = log z, ls = log of
+    transition_loop(2, 1 - switch_prob).  Zeros become -inf: such a move is forbidden."""
+    import numpy as np
+
+    from .sequence import _local_window, transition_loop
+
+    h = W // 2
+    row = np.zeros(n_bins, np.float64)
+    lpad = (n_bins - W) // 2
+    row[lpad:lpad + W] = _local_window("triangle", W)
+    row = np.roll(row, n_bins // 2 + 1)                         # the row of state 0 before transition_local cuts it
+    d = np.arange(-h, h + 1)
+    u = row[d % n_bins]
+    j = np.arange(n_bins)[:, None] + d[None, :]
+    z = np.where((j >= 0) & (j < n_bins), u[None, :], 0.0).sum(axis=1)
+    with np.errstate(divide="ignore"):
+        return _f32(np.log(u)), _f32(np.log(z)), _f32(np.log(transition_loop(2, 1.0 - switch_prob)).reshape(4))
+
+
+def pyin(y, *, fmin, fmax, sr: float = 22050, frame_length: int = 2048, win_length: int | None = None,
+         hop_length: int | None = None, n_thresholds: int = 100, beta_parameters=(2, 18), boltzmann_parameter: float = 2,
+         resolution: float = 0.1, max_transition_rate: float = 35.92, switch_prob: float = 0.01,
+         no_trough_prob: float = 0.01, fill_na=float("nan"), center: bool = True, pad_mode: str = "constant"):
+    """Fundamental frequency per frame with probabilistic YIN (Mauch & Dixon 2014), librosa's signature.
+
+    Every trough of the cumulative-mean-normalised difference (`yin_cmnd`) is a pitch candidate whose probability is
+    summed over `n_thresholds` YIN thresholds weighted by a beta(`beta_parameters`) prior, the troughs that pass a
+    threshold sharing it by a Boltzmann distribution (`boltzmann_parameter`) over their rank; the candidates fall into
+    pitch bins `resolution` semitones wide from fmin to fmax, and a Viterbi decode over (voiced | unvoiced) x bins,
+    pitch moving at most `max_transition_rate` octaves per second and the voicing switching with `switch_prob`, picks
+    the track.  Returns (f0, voiced_flag, voiced_prob): float32 Hz, bool and float32, (n_frames,) or (batch, n_frames)
+    on the input's device; unvoiced frames hold `fill_na` (None: the frequency of the decoded bin).  beta_parameters
+    must be positive integers, win_length None or frame_length // 2.  The definition, with its deviations from librosa
+    (float32 recursion, no parity of numbers claimed), is DESIGN.md 9.17 / tests/pyin_ref.py."""
+    from .cqt import _is_real
+
+    if win_length is not None and win_length != frame_length // 2:
+        raise ValueError(f"win_length must be None or frame_length // 2 = {frame_length // 2}, got {win_length}")
+    if not _is_real(no_trough_prob) or not 0.0 <= float(no_trough_prob) <= 1.0:
+        raise ValueError(f"no_trough_prob must lie in [0, 1], got {no_trough_prob!r}")
+    if fill_na is not None and not _is_real(fill_na):
+        raise ValueError(f"fill_na must be a number or None, got {fill_na!r}")
+    # everything that can be rejected without a device is rejected before one is asked for
+    lo, hi, hop = _yin_lags(fmin, fmax, sr, frame_length, hop_length, pad_mode, "pyin")
+    tab = _pyin_tables(fmin=fmin, fmax=fmax, sr=sr, hop=hop, n_lags=hi - lo + 1, n_thresholds=n_thresholds,
+                       beta_parameters=beta_parameters, boltzmann_parameter=boltzmann_parameter, resolution=resolution,
+                       max_transition_rate=max_transition_rate, switch_prob=switch_prob)
+    lib = _x.lib()
+    if tab["n_bins"] > lib.ap_pyin_max_bins() or tab["W"] > lib.ap_pyin_max_width():
+        raise ValueError(f"pyin: {tab['n_bins']} pitch bins / a transition width of {tab['W']} bins exceed the kernel's caps of "
+                         f"{lib.ap_pyin_max_bins()} / {lib.ap_pyin_max_width()}")
+    y, one_d, lo, hi, hop, center = _yin_setup(y, fmin, fmax, sr, frame_length, hop_length, center, pad_mode, "pyin")
+    B, L = y.shape
+    dev = y.device
+    T = 1 + (L + (2 * (frame_length // 2) if center else 0) - frame_length) // hop
+    if T > _x.lib().ap_viterbi_max_steps():
+        raise ValueError(f"pyin: {T} frames are above the decoder's cap of {_x.lib().ap_viterbi_max_steps()}")
+    nb, n_lags = tab["n_bins"], hi - lo + 1
+    f0 = torch.empty((B, T), dtype=torch.float32, device=dev)
+    voiced = torch.empty((B, T), dtype=torch.uint8, device=dev)
+    vprob = torch.empty((B, T), dtype=torch.float32, device=dev)
+    if B > 0:
+        from .sequence import _on_device_cached
+
+        names = ("thr", "beta", "ea", "nz", "lw", "lz", "ls", "freq")
+        t = dict(zip(names, _on_device_cached(tuple(tab[k] for k in names), dev)))
+        d, st = _x.dlib(dev), _x.stream_ptr(dev)
+        curve = torch.empty((B, n_lags, T), dtype=torch.float32, device=dev)
+        _yin_call("ap_yin_cmnd_f32", y, frame_length, hop,
+                  lambda tw: (_x.ptr(y), B, L, frame_length, hop, int(center), lo, hi, tw, _x.ptr(curve), st))
+        E = torch.empty((B, T, nb + 1), dtype=torch.float32, device=dev)
+        _x.check(d.ap_pyin_observe_f32(_x.ptr(curve), B, n_lags, T, lo, float(sr), float(fmin), tab["bps"], nb, _x.ptr(t["thr"]),
+                                       _x.ptr(t["beta"]), int(n_thresholds), _x.ptr(t["ea"]), _x.ptr(t["nz"]), int(t["ea"].numel()),
+                                       float(no_trough_prob), _x.ptr(E), _x.ptr(vprob), st))
+        ptr = torch.empty((B, T, 2 * nb), dtype=torch.int16, device=dev)       # uint16 scratch
+        states = torch.empty((B, T), dtype=torch.int32, device=dev)
+        logp = torch.empty((B,), dtype=torch.float64, device=dev)
+        _x.check(d.ap_pyin_decode_f32(_x.ptr(E), B, nb, T, _x.ptr(t["lw"]), tab["h"], _x.ptr(t["lz"]), _x.ptr(t["ls"]), tab["li"],
+                                      _x.ptr(t["freq"]), int(fill_na is not None), 0.0 if fill_na is None else float(fill_na),
+                                      _x.ptr(ptr), _x.ptr(states), _x.ptr(f0), _x.ptr(voiced), _x.ptr(logp), 0, st))
+    voiced = voiced.bool()
+    return (f0[0], voiced[0], vprob[0]) if one_d else (f0, voiced, vprob)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
